@@ -18,7 +18,13 @@ each with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, and exits with their st
 torch.distributed.run it is one rank.  --harness-cpu runs the same multi-rank harness with the
 CPU oracle as the step over gloo (a test of the harness, never a measurement).
 
-Extra fields: roofline of the dominant kernel, its algorithmic bytes per launch from SURVEY
+A plain run (--gpus N --steps K --warmup W) sets up, warms up, times the K steps, writes
+--dump-outputs DIR if given (the last timed step's idx / T / nmatch / ninliers / status as
+DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output) and prints
+the headline line.  Everything below is behind --full, after the headline and outside its timing.
+
+--full adds the oracle / pose checks of the timed outputs and the extra fields: roofline of the
+dominant kernel, its algorithmic bytes per launch from SURVEY
 §8(d) (2 x n x 1 KiB + n x 8 B per pair) and its average launch duration measured with HIP events
 on the launch stream over a second, profiled run of the same steps (the headline loop itself runs
 unprofiled); traffic = HBM bytes per launch from the committed rocprofv3 PMC summary of this
@@ -53,6 +59,17 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run everything else this script measures or checks: the "
+                         "profiled loop (roofline, stage split), with_scores, the oracle and pose checks, the CPU "
+                         "baselines and the secondary lines.  Without it the run sets up, warms up, times --steps "
+                         "steps, writes --dump-outputs and prints the headline line; the options below that "
+                         "size those extras (--check, --score-steps, --extra-steps, --window-steps, "
+                         "--cpu-seconds, --no-cpu-baseline) then have no effect")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned (idx, T, nmatch, ninliers, "
+                         "status of its batch) as DIR/<name>.npy in float32, at most 64 MB in all (beyond that a "
+                         "fixed seeded sample of the pairs, listed in DIR/pairs.npy); ranks > 0 write DIR/rank<r>/")
     ap.add_argument("--batch", type=int, default=8192,
                     help="frame-pairs per GPU per step (one launch each; SURVEY §8d: >= 1000 pairs per launch)")
     ap.add_argument("--kp", type=int, default=1024, help="keypoints per frame")
@@ -97,7 +114,10 @@ def parse(argv=None):
     ap.add_argument("--rank-grace", type=float, default=5.0,
                     help="spawned ranks: seconds the surviving ranks get after one rank fails before they are "
                          "terminated (they are blocked in the step's all-gather by then)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def pair_seed(rank, b):
@@ -605,6 +625,32 @@ def roofline(kernel, screen, B, n, avg_s, fused):
                           "fp16" if screen == "f16" else "int8")}}
 
 
+DUMP_BUDGET = 64 << 20  # bytes --dump-outputs may write in all
+
+
+def dump_outputs(torch, path, arrays, budget=DUMP_BUDGET, seed=20240607):
+    """--dump-outputs: the per-pair outputs of the last timed step (`arrays`: name -> tensor whose
+    first axis is the pair) as path/<name>.npy in float32 (int32 values below 2^24 are exact
+    there).  When they exceed `budget` bytes, only a fixed, seeded sample of the pairs (sorted,
+    the same for every run with the same batch) is written, and path/pairs.npy lists them."""
+    os.makedirs(path, exist_ok=True)
+    B = next(iter(arrays.values())).shape[0]
+    per_pair = sum(4 * a[0].numel() for a in arrays.values())
+    keep = None
+    budget -= 4096  # the .npy headers
+    if per_pair * B > budget:
+        k = max(1, (budget - 4 * B) // per_pair)
+        keep = np.sort(np.random.default_rng(seed).choice(B, size=k, replace=False))
+        np.save(os.path.join(path, "pairs.npy"), keep.astype(np.float32))
+    for name, a in arrays.items():
+        if keep is not None:
+            a = a[torch.from_numpy(keep).to(a.device)]
+        h = a.cpu().numpy()
+        if h.dtype != np.float32:
+            assert np.abs(h).max(initial=0) < (1 << 24), name
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(h, dtype=np.float32))
+
+
 def main_cpu_harness(args, world, rank):
     """--harness-cpu: the multi-rank harness (spawn, barrier-bracketed timing, max over ranks,
     per-step result all-gather, JSON) with the CPU oracle as the step -- over gloo."""
@@ -750,6 +796,27 @@ def main():
     elapsed = timed_loop(step, args.steps, args.warmup, sync, barrier)
     elapsed = max_over_ranks(torch, dist, elapsed, coll_dev)
     gathers_timed = gather.count
+
+    if args.dump_outputs:  # what the last timed step returned, before anything below reuses the buffers
+        c = (turn[0] - 1) % P
+        dump_outputs(torch, args.dump_outputs if rank == 0 else os.path.join(args.dump_outputs, "rank%d" % rank),
+                     {"idx": idxs[c], "T": Ts[c], "nmatch": nmatches[c], "ninliers": ninls[c], "status": statuses[c]})
+
+    if not args.full:  # the plain run: the headline and nothing else
+        if rank == 0:
+            print(json.dumps({
+                "metric": METRIC, "value": round(B * args.steps * world / elapsed, 2), "unit": "pairs/s",
+                "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+                "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
+                "vs_baseline": None, "dtype": "f32", "screen": ctxs[0].allpairs_screen(),
+                "config": {"pairs_per_gpu_per_step": B, "kp": n, "dim": KD, "hypotheses": args.hypotheses,
+                           "noise": args.noise, "pipeline": P},
+                "full": False}), flush=True)
+        for cx in ctxs:
+            cx.close()
+        if gather.active:
+            dist.destroy_process_group()
+        return
 
     # per-kernel durations for the roofline and the stage split: a second, profiled loop of the
     # same steps on ONE context (hipEvents on each kernel's own launch stream; with P > 1 the

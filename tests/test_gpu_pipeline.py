@@ -115,7 +115,7 @@ def test_bench_two_ranks_on_the_hip_path():
         env.pop(k, None)
     B = 256
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dist-backend", "gloo",
-                        "--batch", str(B), "--steps", "3", "--warmup", "1", "--extra-steps", "0", "--score-steps", "2",
+                        "--full", "--batch", str(B), "--steps", "3", "--warmup", "1", "--extra-steps", "0", "--score-steps", "2",
                         "--window-steps", "0", "--no-cpu-baseline", "--check", "2"],
                        capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -209,7 +209,7 @@ def test_bench_rccl_result_gather_one_rank():
         env.pop(k, None)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     B = 256
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--force-gather",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--force-gather", "--full",
                         "--dist-backend", "nccl", "--batch", str(B), "--steps", "4", "--warmup", "1",
                         "--extra-steps", "0", "--score-steps", "2", "--window-steps", "0", "--no-cpu-baseline",
                         "--check", "2"], capture_output=True, text=True, timeout=300, env=env)

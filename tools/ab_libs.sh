@@ -6,7 +6,7 @@ set -eu -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 out=gpurun_out/${TAG:-ab}
 mkdir -p "$out"
-ARGS=${ARGS:-"--steps 20 --warmup 3 --no-cpu-baseline --check 1 --extra-steps 0 --window-steps 0 --score-steps 0"}
+ARGS=${ARGS:-"--full --steps 20 --warmup 3 --no-cpu-baseline --check 1 --extra-steps 0 --window-steps 0 --score-steps 0"}
 for r in $(seq 1 ${ROUNDS:-2}); do
   for lib in ${LIBS}; do
     n=$(basename $lib .so)

@@ -9,7 +9,7 @@ A="--steps 20 --warmup 3 --extra-steps 0 --window-steps 0 --score-steps 0 --no-c
 for r in 1 2; do
   for mode in "--force-gather --gather-every 1" "--force-gather" ""; do
     tag=$(echo "x$mode" | tr -d ' -')
-    timeout -k 10 300 python -u bench.py $mode $A > "$out/$tag.json" 2> "$out/$tag.err" || { tail -20 "$out/$tag.err"; exit 1; }
+    timeout -k 10 300 python -u bench.py --full $mode $A > "$out/$tag.json" 2> "$out/$tag.err" || { tail -20 "$out/$tag.err"; exit 1; }
     python3 -c "import json; d=json.loads(open('$out/$tag.json').read().strip().splitlines()[-1]); g=d.get('result_gather') or {}; print('round $r [$mode]', d['value'], d['ms_per_step'], 'k', d['roofline']['avg_launch_ms'], 'gathers', g.get('gathers_in_timed_steps'), g.get('steps_per_gather'))"
   done
 done

@@ -1,13 +1,14 @@
 #!/bin/bash
 # A/B of the whole library built with -fno-slp-vectorize (build_variants/libmaveric_allnoslp.so)
-# against the shipped build: bench.py without the CPU baseline, alternated twice.
+# against the shipped build: bench.py --full without the CPU baseline, alternated twice.
 set -u
-mkdir -p gpurun_out
+out=${OUT_DIR:-ab_tmp}
+mkdir -p "$out"
 for i in $(seq ${N_AB:-2}); do
   for v in default allnoslp; do
     if [ $v = default ]; then L=""; else L="build_variants/libmaveric_$v.so"; fi
-    MV_LIB=$L timeout -k 10 400 python bench.py --no-cpu-baseline > gpurun_out/r05am_${v}_$i.json 2> gpurun_out/r05am_${v}_$i.err || exit 1
-    python3 - gpurun_out/r05am_${v}_$i.json $v <<'PY'
+    MV_LIB=$L timeout -k 10 400 python bench.py --full --no-cpu-baseline > "$out/allnoslp_${v}_$i.json" 2> "$out/allnoslp_${v}_$i.err" || exit 1
+    python3 - "$out/allnoslp_${v}_$i.json" $v <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])
 out = [sys.argv[2], "headline %.0f" % d["value"], str(d["stages_ms_per_step"])]

@@ -5,7 +5,7 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 TAG=${1:-r01}
-ARGS=${PROF_BENCH_ARGS:-"--steps 10 --warmup 2 --no-cpu-baseline --check 0"}
+ARGS=${PROF_BENCH_ARGS:-"--full --steps 10 --warmup 2 --no-cpu-baseline --check 0"}
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp

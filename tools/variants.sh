@@ -7,7 +7,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 export PYTHONUNBUFFERED=1
 BENCH=${BENCH:-bench.py}
-ARGS=${BENCH_ARGS:-"--steps 20 --warmup 3 --no-cpu-baseline --check 1"}
+ARGS=${BENCH_ARGS:-"--full --steps 20 --warmup 3 --no-cpu-baseline --check 1"}
 IFS=';' read -ra VS <<< "${VARIANTS:-}"
 i=0
 for V in "${VS[@]}"; do
