@@ -175,6 +175,15 @@ def lib():
             "mv_local_feature_pool_load_factor": (_F, [_P]),
             "mv_local_feature_pool_check_invariant": (_I, [_P, _I]),
             "mv_local_feature_pool_track_frame": (_I, [_P, _I, _I, _P]),
+            "mv_vocabulary_create": (_I, [_P, _I, _I, _P, _P, _P, _P, ctypes.POINTER(_P)]),
+            "mv_vocabulary_destroy": (_I, [_P]),
+            "mv_bow_words_batch_dev": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+            "mv_bow_words_host": (_I, [_P, _P, _I, _F, _P, _I, _P, _P, _P, _P, _P, _P]),
+            "mv_word_set_stride": (_I, [_I]),
+            "mv_word_sets_batch_dev": (_I, [_P, _I, _I, _I, _P, _P, _P]),
+            "mv_lcd_overlap_dev": (_I, [_P, _I, _I, _P, _I, _P, _P]),
+            "mv_lcd_best_dev": (_I, [_P, _I, _I, _P, _I, _P, _P, _P, _P]),
+            "mv_lcd_overlap_sorted_host": (_I, [_P, _I, _I, _I, _P, _P, _I, _P, _P]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -690,6 +699,197 @@ class Context:
         check(lib().mv_pose_from_matches_dev(self.h, ctypes.byref(params), B, cap, _t(n0), _t(match_idx), _t(kp0),
                                              _t(kp1), _t(T), _t(num_matches), _t(num_inliers), _t(status)),
               "pose_from_matches")
+
+    # ---------------- loop closure (include/loop_closure.h) ----------------
+    def bow_words(self, voc, desc_scales, desc, num_sel, patches, base, wid, word_id, best_match, scores=None):
+        """Device tensors: desc [B, cells, 256] int8, desc_scales / num_sel [B], patches [B, N];
+        outputs [B, N] int32 and scores [B, N, nb] float32 (or None)."""
+        B, cells, N = desc.shape[0], desc.shape[1], patches.shape[1]
+        check(lib().mv_bow_words_batch_dev(self.h, voc.h, B, cells, N, _t(desc_scales), _t(desc), _t(num_sel),
+                                           _t(patches), _t(base), _t(wid), _t(word_id), _t(best_match), _t(scores)),
+              "bow_words")
+
+    def bow_words_host(self, voc, desc_scale, desc, patches, want_scores=True):
+        """One frame, numpy in and out -> dict(base, wid, word_id, best_match[, scores])."""
+        desc = np.ascontiguousarray(desc, np.int8)
+        patches = np.ascontiguousarray(patches, np.int32)
+        n = patches.size
+        out = {k: np.zeros(n, np.int32) for k in ("base", "wid", "word_id", "best_match")}
+        sc = np.zeros((n, voc.num_base), np.float32) if want_scores else None
+        check(lib().mv_bow_words_host(self.h, voc.h, desc.shape[0], float(desc_scale), _np(desc), n, _np(patches),
+                                      _np(out["base"]), _np(out["wid"]), _np(out["word_id"]), _np(out["best_match"]),
+                                      _np(sc) if want_scores else None), "bow_words_host")
+        if want_scores:
+            out["scores"] = sc
+        return out
+
+    def word_sets(self, num_words, word_id, bits, distinct):
+        """word_id [B, N] int32 -> bits [B, word_set_stride(num_words)] int32, distinct [B]."""
+        B, N = word_id.shape[0], word_id.shape[1]
+        check(lib().mv_word_sets_batch_dev(self.h, num_words, B, N, _t(word_id), _t(bits), _t(distinct)), "word_sets")
+
+    def lcd_overlap(self, num_words, q_bits, db_bits, counts):
+        """counts [Q, F] int32 = popcount(q_bits[q] & db_bits[f])."""
+        check(lib().mv_lcd_overlap_dev(self.h, num_words, q_bits.shape[0], _t(q_bits), db_bits.shape[0], _t(db_bits),
+                                       _t(counts)), "lcd_overlap")
+
+    def lcd_best(self, num_words, q_bits, db_bits, limit, best_frame, best_count, F=None):
+        """Per query the best database frame f < min(limit[q], F) (lowest f on ties; (-1, 0) when
+        none).  F: the rows of db_bits in use (default: all)."""
+        check(lib().mv_lcd_best_dev(self.h, num_words, q_bits.shape[0], _t(q_bits),
+                                    db_bits.shape[0] if F is None else F, _t(db_bits), _t(limit), _t(best_frame),
+                                    _t(best_count)), "lcd_best")
+
+    def lcd_overlap_sorted_host(self, num_words, prev_lists, cur_list):
+        """lcd_main.c's shape: strictly ascending id lists of F previous frames and the current
+        one -> counts [F] (sets built and compared on the device)."""
+        F = len(prev_lists)
+        cap = max([len(p) for p in prev_lists] + [len(cur_list), 1])
+        prev_n = np.array([len(p) for p in prev_lists], np.int32)
+        prev = np.full((F, cap), -1, np.int32)
+        for f, p in enumerate(prev_lists):
+            prev[f, :len(p)] = p
+        cur = np.ascontiguousarray(cur_list, np.int32)
+        counts = np.zeros(F, np.int32)
+        check(lib().mv_lcd_overlap_sorted_host(self.h, num_words, F, cap, _np(prev_n), _np(prev), cur.size, _np(cur),
+                                               _np(counts)), "lcd_overlap_sorted_host")
+        return counts
+
+
+# ---------------- loop closure: vocabulary and place database ----------------
+VOCABULARY_FIELDS = ("num_base", "words_per_base", "scale", "bias", "base_desc", "leaf")
+
+
+def word_set_stride(num_words):
+    """uint32 words per bitset row (a multiple of 4: rows are read 128 bits at a time)."""
+    return lib().mv_word_set_stride(int(num_words))
+
+
+def _c_int(tok):
+    t = tok.strip().lower()
+    return int(t[2:], 2) if t.startswith("0b") else int(t)
+
+
+def vocabulary_from_header(path):
+    """The arrays of a vocabulary.h-format header (include/data/LCD/vocabulary.h: `const T
+    name[dims] = {literals};` with decimal and 0b... literals) as a dict of VOCABULARY_FIELDS.
+    A text parser of the data format only -- nothing is compiled or executed.  Integer literals
+    wrap to the declared type as a C compiler wraps them (int8_t 243 -> -13)."""
+    import re
+
+    src = open(path).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    src = re.sub(r"//[^\n]*", "", src)
+    decl = {}
+    for m in re.finditer(r"const\s+(\w+)\s+(\w+)\s*((?:\[\s*\d+\s*\])*)\s*=\s*([^;]*);", src):
+        ctype, name, dims, body = m.groups()
+        shape = tuple(int(d) for d in re.findall(r"\d+", dims))
+        toks = [t for t in re.split(r"[\s,{}]+", body) if t]
+        if ctype == "float":
+            val = np.array([float(t.rstrip("fF")) for t in toks], np.float64).astype(np.float32)
+        else:
+            val = np.array([_c_int(t) for t in toks], np.int64)
+        n = int(np.prod(shape)) if shape else 1
+        if val.size != n:
+            raise MVError("%s: %d values for shape %s" % (name, val.size, shape))
+        decl[name] = val.reshape(shape) if shape else val.reshape(())
+    need = ("num_base_nodes", "scale_arr", "bias_arr", "base_descriptors", "words_per_base_node", "leaf_descriptors")
+    for k in need:
+        if k not in decl:
+            raise MVError("%s: no %s" % (path, k))
+    nb, wpb = int(decl["num_base_nodes"]), int(decl["words_per_base_node"])
+    out = {"num_base": np.int32(nb), "words_per_base": np.int32(wpb),
+           "scale": decl["scale_arr"].astype(np.float32), "bias": decl["bias_arr"].astype(np.float32),
+           "base_desc": (decl["base_descriptors"] & 0xFF).astype(np.uint8).view(np.int8),
+           "leaf": (decl["leaf_descriptors"] & 0xFFFFFFFF).astype(np.uint32)}
+    if (out["scale"].shape != (nb,) or out["bias"].shape != (nb,) or out["base_desc"].shape != (256, nb)
+            or out["leaf"].shape != (nb, wpb, 4)):
+        raise MVError("%s: array shapes do not fit num_base_nodes = %d, words_per_base_node = %d" % (path, nb, wpb))
+    return out
+
+
+class Vocabulary:
+    """A vocabulary on the device (mv_vocabulary_*): owns the handle, close() / __del__ like SuperPoint."""
+
+    def __init__(self, ctx, arrays):
+        self.num_base, self.words_per_base = int(arrays["num_base"]), int(arrays["words_per_base"])
+        self.num_words = self.num_base * self.words_per_base
+        sc = np.ascontiguousarray(arrays["scale"], np.float32)
+        bi = np.ascontiguousarray(arrays["bias"], np.float32)
+        bd = np.ascontiguousarray(arrays["base_desc"], np.int8)
+        lf = np.ascontiguousarray(arrays["leaf"], np.uint32)
+        if (sc.shape != (self.num_base,) or bi.shape != (self.num_base,) or bd.shape != (256, self.num_base)
+                or lf.shape != (self.num_base, self.words_per_base, 4)):
+            raise MVError("vocabulary: array shapes do not fit num_base / words_per_base")
+        h = _P()
+        check(lib().mv_vocabulary_create(ctx.h, self.num_base, self.words_per_base, _np(sc), _np(bi), _np(bd), _np(lf),
+                                         ctypes.byref(h)), "vocabulary_create")
+        self.h, self.ctx = h, ctx
+
+    def close(self):
+        if self.h:
+            lib().mv_vocabulary_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def load_vocabulary(npz_path):
+    """dict of VOCABULARY_FIELDS from an .npz of that layout (tests/golden/vocabulary.npz)."""
+    d = np.load(npz_path, allow_pickle=False)
+    return {k: d[k] for k in VOCABULARY_FIELDS}
+
+
+class PlaceDatabase:
+    """A preallocated device ring of frame word sets [capacity][stride]: add(bits_row) -> index,
+    query(bits, min_gap) -> (best_frame, best_count) among the frames added at least min_gap
+    before the newest (limit = size - min_gap).  Runs on the context's current stream."""
+
+    def __init__(self, ctx, num_words, capacity):
+        import torch
+
+        self.ctx, self.num_words, self.capacity = ctx, int(num_words), int(capacity)
+        self.stride = word_set_stride(num_words)
+        if self.stride <= 0 or self.capacity <= 0:
+            raise MVError("PlaceDatabase: num_words and capacity must be positive")
+        self.dev = torch.device("cuda:%d" % ctx.device)
+        self.bits = torch.zeros((self.capacity, self.stride), dtype=torch.int32, device=self.dev)
+        self.size = 0
+        self._limit = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        self._best = torch.zeros(2, dtype=torch.int32, device=self.dev)
+
+    def _stream(self):
+        import torch
+
+        h = lib().mv_context_stream(self.ctx.h)  # None: HIP's null stream, torch's default stream
+        return torch.cuda.ExternalStream(h, device=self.dev) if h else torch.cuda.default_stream(self.dev)
+
+    def add(self, bits_row):
+        import torch
+
+        if self.size >= self.capacity:
+            raise MVError("PlaceDatabase is full (%d frames)" % self.capacity)
+        with torch.cuda.stream(self._stream()):
+            self.bits[self.size].copy_(bits_row.reshape(self.stride), non_blocking=True)
+        self.size += 1
+        return self.size - 1
+
+    def query(self, bits, min_gap=0):
+        import torch
+
+        if self.size == 0:
+            return -1, 0
+        q = bits.reshape(1, self.stride)
+        with torch.cuda.stream(self._stream()):
+            self._limit.fill_(self.size - int(min_gap))
+            self.ctx.lcd_best(self.num_words, q, self.bits, self._limit, self._best[0:1], self._best[1:2],
+                              F=self.size)
+            bf, bc = self._best.cpu().tolist()
+        return bf, bc
 
 
 # ---------------- quantized SuperPoint front-end (include/superpoint.h) ----------------
