@@ -838,7 +838,7 @@ __device__ __forceinline__ unsigned epilogue_t(char *epi, const float2 *rowv, co
         const bool live = rl < n0;
         const float2 rv = rowv[rl];
         float bs = -__builtin_inff();
-        int bj = 0x7fffffff, need = -1;
+        int bj = NO_COLUMN, need = -1;
         bool wide = live && rv.y < 0.f;  // a row outside the int8 range: every column
         bool rescan = false;             // wide, re-screened (rescan_t) against limit lim_k
         int lim_k = 0;
@@ -939,7 +939,7 @@ __device__ __forceinline__ unsigned epilogue_t(char *epi, const float2 *rowv, co
     for (int g = 0; g < T_RG; g++)
         if (out_g[g]) {
             const int rl = w * (32 * T_RG) + g * 32 + fr;
-            const bool keep = bj_g[g] != 0x7fffffff && (double)bs_g[g] > thresh && bs_g[g] > 0.f;
+            const bool keep = bj_g[g] != NO_COLUMN && (double)bs_g[g] > thresh && bs_g[g] > 0.f;
             oidx[rl] = keep ? bj_g[g] : -1;
             if (oscore) oscore[rl] = keep ? bs_g[g] : 0.f;
         }
@@ -956,7 +956,7 @@ __device__ __forceinline__ unsigned epilogue_t(char *epi, const float2 *rowv, co
             }
             const float *a = A + (size_t)r * KD;
             float ws = -__builtin_inff();
-            int wj = 0x7fffffff;
+            int wj = NO_COLUMN;
             for (int j = lane; j < n1; j += 64) {
                 if (!((wm >> ((j >> 2) & 1)) & 1u)) continue;
                 const float *ap = a;
@@ -977,7 +977,7 @@ __device__ __forceinline__ unsigned epilogue_t(char *epi, const float2 *rowv, co
                 }
             }
             if (lane == 0) {
-                const bool keep = wj != 0x7fffffff && (double)ws > thresh && ws > 0.f;
+                const bool keep = wj != NO_COLUMN && (double)ws > thresh && ws > 0.f;
                 oidx[r] = keep ? wj : -1;
                 if (oscore) oscore[r] = keep ? ws : 0.f;
             }
@@ -1147,7 +1147,7 @@ __global__ __launch_bounds__(64 * RS_NW) void k_q8t_rescan(int batch, int cap, c
             const int lim = lims[min(fr, ns - 1)];
             int cnt = 0;
             float bs = -__builtin_inff();
-            int bj = 0x7fffffff;
+            int bj = NO_COLUMN;
             auto flush = [&]() {  // exact scores of the listed columns, one list position per round
                 for (int k = 0; __ballot(k < cnt); k++) {
                     const int j = k < cnt ? mycl[k] : -1;
@@ -1220,7 +1220,7 @@ __global__ __launch_bounds__(64 * RS_NW) void k_q8t_rescan(int batch, int cap, c
                         bs = red_s[v][fr];
                         bj = red_j[v][fr];
                     }
-                const bool keep = bj != 0x7fffffff && (double)bs > thresh && bs > 0.f;
+                const bool keep = bj != NO_COLUMN && (double)bs > thresh && bs > 0.f;
                 oidx[myrow] = keep ? bj : -1;
                 if (oscore) oscore[myrow] = keep ? bs : 0.f;
             }

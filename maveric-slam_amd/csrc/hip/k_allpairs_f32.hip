@@ -1,5 +1,6 @@
 // k_allpairs_f32.hip -- all-pairs fp32 descriptor match (python/pairwise_pnp.py:635-659)
-// with the gemmini_functions_cpu.h:14-56 summation order as the exact score.
+// with the gemmini_functions_cpu.h:14-56 summation order as the exact score: the fp16 screen's
+// kernels and their two launchers (the entry points and the screen dispatch: mv_allpairs.hip).
 //
 // Two kernels per batch (plus a 4-byte-per-pair memset):
 //   k_ap_split  one pass over both frames: every fp32 descriptor row becomes an fp16 row of
@@ -43,7 +44,9 @@
 
 #include <algorithm>
 
+#include "ap_exact.hpp"
 #include "mv_internal.hpp"
+#include "mv_wave.hpp"
 
 namespace {
 
@@ -71,110 +74,8 @@ constexpr int OFF_MISC = OFF_ANRM + BM * 4;      // [NW] f32 per-wave max|b|^2
 constexpr int LDS_BYTES = OFF_MISC + 4 * NW;
 static_assert(LDS_BYTES * (8 / NW) <= 160 * 1024, "LDS per CU");
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-
-// 16-B-per-lane HBM/L2 -> LDS DMA (global_load_lds_dwordx4, SADDR form): source = SGPR
-// base + 32-bit VGPR byte offset; LDS destination = M0 (wave-uniform byte address) + lane *
-// 16.  No instruction offset: it would displace the LDS destination as well.  The constant
-// K offset (KOFF) and LDS offset (DOFF) are added INSIDE the asm, so the compiler cannot
-// hoist one address per slice into long-lived registers.
-// (the m0 clobber warning fires at template instantiation: ignored for the whole file)
-#pragma clang diagnostic ignored "-Winline-asm"
-template <int KOFF, int DOFF>
-__device__ __forceinline__ void glds16(const void *sbase, unsigned voff, unsigned lds_byte) {
-    unsigned tmp;
-    asm volatile(
-        "v_add_u32 %0, %4, %1\n\t"
-        "s_add_u32 m0, %3, %5\n\t"
-        "global_load_lds_dwordx4 %0, %2"
-        : "=&v"(tmp)
-        : "v"(voff), "s"(sbase), "s"(lds_byte), "i"(KOFF), "i"(DOFF)
-        : "memory", "m0", "scc");
-}
-
-// s_waitcnt on vmcnt only (expcnt / lgkmcnt left at their no-wait maxima)
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    static_assert(N >= 0 && N < 64, "vmcnt is 6 bits");
-    __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));
-}
-
-// (f & keep) | tag in one instruction (keep in a VGPR: one SGPR operand only)
-__device__ __forceinline__ float tagf(float f, unsigned keep, unsigned tag) {
-    float r;
-    asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(f), "v"(keep), "s"(tag));
-    return r;
-}
-// top-2 of {m1, m2, a, b} given m1 >= m2: m1' = max3(m1, a, b), m2' = max(m2, med3(m1, a, b))
-__device__ __forceinline__ void fold3(float a, float b, float &m1, float &m2) {
-    float md;
-    asm("v_med3_f32 %0, %1, %2, %3" : "=v"(md) : "v"(m1), "v"(a), "v"(b));
-    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(m1) : "v"(m1), "v"(a), "v"(b));
-    asm("v_max_f32 %0, %1, %2" : "=v"(m2) : "v"(m2), "v"(md));
-}
-
-// xor-shuffles within 32 lanes by ds_swizzle (immediate pattern: no lane-address VGPRs)
-template <int M>
-__device__ __forceinline__ float swz_xor(float v) {
-    static_assert(M >= 0 && M < 32, "ds_swizzle bit mode stays within 32 lanes");
-    return __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), (M << 10) | 0x1F));
-}
-template <int M>
-__device__ __forceinline__ int swz_xor(int v) {
-    static_assert(M >= 0 && M < 32, "ds_swizzle bit mode stays within 32 lanes");
-    return __builtin_amdgcn_ds_swizzle(v, (M << 10) | 0x1F);
-}
-
-// XCD-aware bijective remap: blocks b and b+8 share an XCD (round-robin dispatch); give
-// each XCD a contiguous run of logical blocks so a pair's row tiles share one L2.  Speed only.
-__device__ __forceinline__ int xcd_remap(int b, int total) {
-    const int q = total / 8, r = total % 8, x = b % 8;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + b / 8;
-}
-
-
-// nn_match_two_way's distance (pairwise_pnp.py:303): sqrt(2 - 2 clip(dot, -1, 1)) in float32
-// (np.clip keeps NaN); IEEE sqrt
-__device__ __forceinline__ float dist_of(float e) {
-    const float c = e != e ? e : fminf(fmaxf(e, -1.f), 1.f);
-    return sqrtf(__fsub_rn(2.f, __fmul_rn(2.f, c)));
-}
-// is (v, j) a better candidate than (bv, bj)?  dmode 0: larger dot, ties to the smaller index
-// (NaN never wins: `score > max_score`); dmode 1: np.argmin -- the first NaN, else the smaller
-// distance, ties to the smaller index
-__device__ __forceinline__ bool better(int dmode, float v, int j, float bv, int bj) {
-    if (!dmode) return v > bv || (v == bv && j < bj);
-    const bool nv = v != v, nb = bv != bv;
-    if (nv || nb) return nv && (!nb || j < bj);
-    return v < bv || (v == bv && j < bj);
-}
-
-// The reference's sequential fp32 dot (mul then add, k = 0..255).  Latency-bound: loads go
-// out U = 16 float4 per operand at a time (four round trips per dot).
-__device__ __forceinline__ float exact_dot(const float *__restrict__ a, const float *__restrict__ b) {
-    constexpr int U = 16;
-    float s = 0.f;
-#pragma unroll
-    for (int bt = 0; bt < KD / (4 * U); bt++) {
-        float4 xa[U], xb[U];
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            xa[u] = *reinterpret_cast<const float4 *>(a + 4 * U * bt + 4 * u);
-            xb[u] = *reinterpret_cast<const float4 *>(b + 4 * U * bt + 4 * u);
-        }
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const float4 x = xa[u], y = xb[u];
-            s = __fadd_rn(s, __fmul_rn(x.x, y.x));
-            s = __fadd_rn(s, __fmul_rn(x.y, y.y));
-            s = __fadd_rn(s, __fmul_rn(x.z, y.z));
-            s = __fadd_rn(s, __fmul_rn(x.w, y.w));
-        }
-    }
-    return s;
-}
+using namespace wave;
+using namespace ap_exact;
 
 // ---- k_ap_split: frame 1 only.  32 lanes per row: lane l converts floats 4l .. 4l+3 and
 //      128 + 4l .. +3 (each load instruction reads 512 contiguous bytes of two rows; each
@@ -183,7 +84,6 @@ __device__ __forceinline__ float exact_dot(const float *__restrict__ a, const fl
 //      never read downstream) ----
 constexpr int SPLIT_RPG = 4;
 constexpr int SPLIT_ROWS = 8 * SPLIT_RPG;  // rows per block iteration: 8 row groups x SPLIT_RPG
-typedef float f32x4v __attribute__((ext_vector_type(4)));
 // waves per EU: 8 (with SPLIT_RPG 2: 46 VGPRs) lets split waves co-reside with two k_ap_match
 // waves; measured: 0.34 -> 0.44 ms beside the pose, and the overlapped pipeline (bench
 // --pipeline 2/3) only +2 %: 1 kept
@@ -290,11 +190,11 @@ __global__ __launch_bounds__(NT, 8 / NW) void k_ap_match(int tiles_r, int cap, c
     const unsigned dst_w = lds_base + (unsigned)(wu * RPW * SL_ROW);
 #define AP_STAGE(SLOT, KSI)                                                                  \
     do {                                                                                     \
-        glds16<(KSI) * SL_ROW, (SLOT) * SL_BYTES>(SB, oB[0], dst_w);                         \
-        glds16<(KSI) * SL_ROW, (SLOT) * SL_BYTES + 4 * SL_ROW>(SB, oB[1], dst_w);            \
+        glds16_koff<(KSI) * SL_ROW, (SLOT) * SL_BYTES>(SB, oB[0], dst_w);                         \
+        glds16_koff<(KSI) * SL_ROW, (SLOT) * SL_BYTES + 4 * SL_ROW>(SB, oB[1], dst_w);            \
         if constexpr (RPW == 16) {                                                           \
-            glds16<(KSI) * SL_ROW, (SLOT) * SL_BYTES + 8 * SL_ROW>(SB, oB[RPW / 4 - 2], dst_w);  \
-            glds16<(KSI) * SL_ROW, (SLOT) * SL_BYTES + 12 * SL_ROW>(SB, oB[RPW / 4 - 1], dst_w); \
+            glds16_koff<(KSI) * SL_ROW, (SLOT) * SL_BYTES + 8 * SL_ROW>(SB, oB[RPW / 4 - 2], dst_w);  \
+            glds16_koff<(KSI) * SL_ROW, (SLOT) * SL_BYTES + 12 * SL_ROW>(SB, oB[RPW / 4 - 1], dst_w); \
         }                                                                                    \
     } while (0)
 #define AP_TILE_OFFSETS(TC)                                                                  \
@@ -380,7 +280,7 @@ __global__ __launch_bounds__(NT, 8 / NW) void k_ap_match(int tiles_r, int cap, c
     do {                                                                                      \
         const unsigned g0_ = __builtin_amdgcn_readfirstlane(2u * (unsigned)(TC)), g1_ = g0_ + 1u; \
         _Pragma("unroll") for (int q = (Q0); q < (Q1); q++)                                   \
-            fold3(tagf(X0[q], vkeep, g0_), tagf(X1[q], vkeep, g1_), m1[q], m2[q]);            \
+            fold3(tag(X0[q], vkeep, g0_), tag(X1[q], vkeep, g1_), m1[q], m2[q]);            \
     } while (0)
 #define AP_FOLD(X0, X1, TC) AP_FOLD_ROWS(X0, X1, TC, 0, 16)
 #define AP_SLOT(J, C0, C1, F0, F1, FOLD)                                                      \
@@ -518,7 +418,7 @@ __global__ __launch_bounds__(NT, 8 / NW) void k_ap_match(int tiles_r, int cap, c
     // dmode 0: maximum dot (first strict), kept above thresh and 0 (pairwise_pnp.py:639-651);
     // dmode 1: minimum distance sqrt(2 - 2 clip(dot)) (nn_match_two_way, :302-306), no threshold
     float bs = dmode ? __builtin_inff() : -__builtin_inff();
-    int bj = 0x7fffffff;
+    int bj = NO_COLUMN;
     bool wide = live && full;
     // dmode 1: distinct dots can round to one distance; columns within TIE of the maximiser's
     // exact dot are treated as competitors (a distance tie needs |d1 - d2| of a few ulp)
@@ -551,7 +451,7 @@ __global__ __launch_bounds__(NT, 8 / NW) void k_ap_match(int tiles_r, int cap, c
                     const bool sure = !oscore && (dmode || Ms - dp > fmax(thresh, 0.0));
                     // (Ms = M 2^-28 is exact in float, and Ms > thresh, Ms > 0: the keep test passes)
                     bs = sure ? (float)Ms : exact_dot(arow, B + (size_t)I * KD);
-                    if (dmode) bs = sure ? 0.f : dist_of(bs);
+                    if (dmode) bs = sure ? 0.f : dist(bs);
                     bj = I;
                 }
             } else {  // both lanes of the row take this branch
@@ -585,7 +485,7 @@ __global__ __launch_bounds__(NT, 8 / NW) void k_ap_match(int tiles_r, int cap, c
                         const float *ap = arow;
                         asm volatile("" : "+v"(ap));  // keep the A row's loads inside the loop
                         const float e = exact_dot(ap, B + (size_t)j * KD);
-                        const float v = dmode ? dist_of(e) : e;
+                        const float v = dmode ? dist(e) : e;
                         if (better(dmode, v, j, bs, bj)) {
                             bs = v;
                             bj = j;
@@ -604,7 +504,7 @@ __global__ __launch_bounds__(NT, 8 / NW) void k_ap_match(int tiles_r, int cap, c
         }
     }
     if (fh == 0 && live && !wide) {
-        const bool keep = bj != 0x7fffffff && (dmode || ((double)bs > thresh && bs > 0.f));
+        const bool keep = bj != NO_COLUMN && (dmode || ((double)bs > thresh && bs > 0.f));
         oidx[rl] = keep ? bj : -1;
         if (oscore) oscore[rl] = keep ? bs : 0.f;
     }
@@ -615,14 +515,14 @@ __global__ __launch_bounds__(NT, 8 / NW) void k_ap_match(int tiles_r, int cap, c
         const int r = w * RW + __builtin_ctz(dm);
         const float *a = A + (size_t)(row0 + r) * KD;
         float ws = dmode ? __builtin_inff() : -__builtin_inff();
-        int wj = 0x7fffffff;
+        int wj = NO_COLUMN;
         for (unsigned Lm = lmask[r]; Lm; Lm &= Lm - 1) {
             const int f = __builtin_ctz(Lm);
             for (int j = f + 32 * lane; j < n1; j += 32 * 64) {
                 const float *ap = a;
                 asm volatile("" : "+v"(ap));  // keep the A row's loads inside the loop
                 const float e = exact_dot(ap, B + (size_t)j * KD);
-                const float v = dmode ? dist_of(e) : e;
+                const float v = dmode ? dist(e) : e;
                 if (better(dmode, v, j, ws, wj)) {
                     ws = v;
                     wj = j;
@@ -646,7 +546,7 @@ __global__ __launch_bounds__(NT, 8 / NW) void k_ap_match(int tiles_r, int cap, c
         AP_WRED(32);
 #undef AP_WRED
         if (lane == 0) {
-            const bool keep = wj != 0x7fffffff && (dmode || ((double)ws > thresh && ws > 0.f));
+            const bool keep = wj != NO_COLUMN && (dmode || ((double)ws > thresh && ws > 0.f));
             oidx[r] = keep ? wj : -1;
             if (oscore) oscore[r] = keep ? ws : 0.f;
         }
@@ -657,16 +557,8 @@ __global__ __launch_bounds__(NT, 8 / NW) void k_ap_match(int tiles_r, int cap, c
 
 namespace mv {
 
-// scratch: h1 (batch * cap * 512 B) | nrm1 (batch * cap f32) | bad (batch i32); the int8
-// screen's layout (k_allpairs_q8.hip) shares the buffer: the size covers both
-size_t allpairs_f32_scratch_bytes(int batch, int cap) {
-    const size_t rows = (size_t)batch * cap;
-    const size_t f16 = rows * ROW_BYTES + align_up(rows * 4, 256) + align_up((size_t)batch * 4, 256);
-    return std::max(f16, allpairs_q8_scratch_bytes(batch, cap));
-}
-// one staged image under `screen`: fp16 (516 B per row) or int8 (268 B per row)
-size_t ap_image_bytes(int screen, int batch, int cap) {
-    if (screen != MV_SCREEN_F16) return allpairs_q8_scratch_bytes(batch, cap);
+// the image: h1 (batch * cap * 512 B) | nrm1 (batch * cap f32) | bad (batch i32)
+size_t allpairs_f32_image_bytes(int batch, int cap) {
     const size_t rows = (size_t)batch * cap;
     return rows * ROW_BYTES + align_up(rows * 4, 256) + align_up((size_t)batch * 4, 256);
 }
@@ -724,333 +616,3 @@ int launch_allpairs_f32_match(hipStream_t s, void *scratch, int batch, int cap, 
 }
 
 }  // namespace mv
-
-namespace {
-void *ap_scratch(mv_context *ctx, size_t bytes) {
-    if (bytes <= ctx->ap_scratch_bytes) return ctx->ap_scratch;
-    if (ctx->ap_scratch) {
-        (void)mv::quiesce(ctx);  // growing: nothing of this context may still use the old buffer
-        (void)hipFree(ctx->ap_scratch);
-        ctx->ap_scratch = nullptr;
-        ctx->ap_scratch_bytes = 0;
-        ctx->prep_desc1 = nullptr;  // a prepared frame 1 lived in the freed buffer
-    }
-    const size_t b = mv::align_up(bytes, 1 << 20);
-    if (hipMalloc(&ctx->ap_scratch, b) != hipSuccess) {
-        mv::set_error(MV_ERR_OUT_OF_MEMORY, "all-pairs scratch allocation of %zu bytes failed", b);
-        ctx->ap_scratch = nullptr;
-        return nullptr;
-    }
-    ctx->ap_scratch_bytes = b;
-    return ctx->ap_scratch;
-}
-}  // namespace
-
-namespace {
-// staging of frame 1 for the screens that match against an image (fp16, staged int8; the
-// default int8 screen stages only for sequence mode, which reuses the images)
-int ap_prepare(int screen, hipStream_t s, void *scr, int batch, int cap, const int *n1, const float *desc1) {
-    return screen == MV_SCREEN_F16 ? mv::launch_allpairs_f32_prepare(s, scr, batch, cap, n1, desc1)
-                                   : mv::launch_allpairs_q8_prepare(s, scr, batch, cap, n1, desc1);
-}
-// the match; MV_SCREEN_I8 reads both fp32 frames directly (no image, scr unused)
-int ap_match(mv_context *ctx, int screen, hipStream_t s, void *scr, int batch, int cap, const int *n0, const int *n1,
-             const float *desc0, const float *desc1, double thresh, int *match_idx, float *match_score,
-             int dmode = 0) {
-    if (screen == MV_SCREEN_I8) {
-        if (mv::allpairs_q8t_applies(cap, dmode)) {
-            void *fl = mv::scratch(ctx, mv::allpairs_q8t_scratch_bytes(batch));
-            if (!fl) return MV_ERR_OUT_OF_MEMORY;
-            return mv::launch_allpairs_q8t_match(s, fl, batch, cap, n0, n1, desc0, desc1, thresh, match_idx,
-                                                 match_score);
-        }
-        return mv::launch_allpairs_q8d_match(s, batch, cap, n0, n1, desc0, desc1, thresh, match_idx, match_score,
-                                             dmode);
-    }
-    return screen == MV_SCREEN_F16
-               ? mv::launch_allpairs_f32_match(s, scr, batch, cap, n0, n1, desc0, desc1, thresh, match_idx,
-                                               match_score, dmode)
-               : mv::launch_allpairs_q8_match(s, scr, batch, cap, n0, n1, desc0, desc1, thresh, match_idx,
-                                              match_score, dmode);
-}
-}  // namespace
-
-extern "C" int mv_match_allpairs_f32_dev(mv_context *ctx, int batch, int cap, const int *n0, const int *n1,
-                                         const float *desc0, const float *desc1, double thresh, int *match_idx,
-                                         float *match_score) {
-    MV_REQUIRE(ctx != nullptr && batch > 0 && cap > 0);
-    MV_HIP_TRY(hipSetDevice(ctx->device));
-    if (ctx->ap_screen == MV_SCREEN_I8)  // one pass, no image
-        return ap_match(ctx, ctx->ap_screen, ctx->stream, nullptr, batch, cap, n0, n1, desc0, desc1, thresh, match_idx,
-                        match_score);
-    void *scr = ap_scratch(ctx, mv::ap_image_bytes(ctx->ap_screen, batch, cap));
-    if (!scr) return MV_ERR_OUT_OF_MEMORY;
-    ctx->prep_desc1 = nullptr;  // the prepared image is overwritten
-    if (ctx->aux_stream) MV_HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_prep, 0));  // a staging in flight
-    const int st = ap_prepare(ctx->ap_screen, ctx->stream, scr, batch, cap, n1, desc1);
-    if (st != MV_OK) return st;
-    return ap_match(ctx, ctx->ap_screen, ctx->stream, scr, batch, cap, n0, n1, desc0, desc1, thresh, match_idx,
-                    match_score);
-}
-
-extern "C" int mv_match_allpairs_f32_prepare_dev(mv_context *ctx, int batch, int cap, const int *n1,
-                                                 const float *desc1) {
-    MV_REQUIRE(ctx != nullptr && batch > 0 && cap > 0 && n1 && desc1);
-    MV_HIP_TRY(hipSetDevice(ctx->device));
-    if (ctx->ap_screen == MV_SCREEN_I8) {  // the one-pass match reads frame 1 itself: record only
-        ctx->prep_screen = ctx->ap_screen;
-        ctx->prep_staged = false;  // sequence mode stages these frames on first use
-        ctx->prep_batch = batch;
-        ctx->prep_cap = cap;
-        ctx->prep_n1 = n1;
-        ctx->prep_desc1 = desc1;
-        return mv::set_status(MV_OK);
-    }
-    void *scr = ap_scratch(ctx, mv::ap_image_bytes(ctx->ap_screen, batch, cap));
-    if (!scr) return MV_ERR_OUT_OF_MEMORY;
-    if (!ctx->aux_stream) {
-        MV_HIP_TRY(hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking));
-        MV_HIP_TRY(hipEventCreateWithFlags(&ctx->ev_in, hipEventDisableTiming));
-        MV_HIP_TRY(hipEventCreateWithFlags(&ctx->ev_prep, hipEventDisableTiming));
-    }
-    // inputs (and the previous run's use of the scratch) as of this call on the context stream
-    MV_HIP_TRY(hipEventRecord(ctx->ev_in, ctx->stream));
-    MV_HIP_TRY(hipStreamWaitEvent(ctx->aux_stream, ctx->ev_in, 0));
-    const int st = ap_prepare(ctx->ap_screen, ctx->aux_stream, scr, batch, cap, n1, desc1);
-    if (st != MV_OK) return st;
-    MV_HIP_TRY(hipEventRecord(ctx->ev_prep, ctx->aux_stream));
-    ctx->prep_screen = ctx->ap_screen;
-    ctx->prep_staged = true;
-    ctx->prep_batch = batch;
-    ctx->prep_cap = cap;
-    ctx->prep_n1 = n1;
-    ctx->prep_desc1 = desc1;
-    return MV_OK;
-}
-
-extern "C" int mv_match_allpairs_f32_run_dev(mv_context *ctx, int batch, int cap, const int *n0, const int *n1,
-                                             const float *desc0, const float *desc1, double thresh, int *match_idx,
-                                             float *match_score) {
-    MV_REQUIRE(ctx != nullptr);
-    if (!ctx->prep_desc1 || ctx->prep_batch != batch || ctx->prep_cap != cap || ctx->prep_n1 != n1 ||
-        ctx->prep_desc1 != desc1 || ctx->prep_screen != ctx->ap_screen) {
-        mv::set_error(MV_ERR_INVALID_ARG, "mv_match_allpairs_f32_run_dev: no matching prepare for this batch");
-        return MV_ERR_INVALID_ARG;
-    }
-    MV_HIP_TRY(hipSetDevice(ctx->device));
-    if (ctx->prep_staged && ctx->aux_stream) MV_HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_prep, 0));
-    return ap_match(ctx, ctx->ap_screen, ctx->stream, ctx->ap_scratch, batch, cap, n0, n1, desc0, desc1, thresh,
-                    match_idx, match_score);
-}
-
-namespace {
-// the context's second image, grown to `need` bytes (run_prepare's staging target)
-int ap_scratch2(mv_context *ctx, size_t need) {
-    if (ctx->ap_scratch2_bytes >= need) return MV_OK;
-    if (ctx->ap_scratch2) {
-        (void)mv::quiesce(ctx);  // growing: nothing of this context may still use the old buffer
-        (void)hipFree(ctx->ap_scratch2);
-        ctx->ap_scratch2 = nullptr;
-        ctx->ap_scratch2_bytes = 0;
-    }
-    const size_t b = mv::align_up(need, 1 << 20);
-    if (hipMalloc(&ctx->ap_scratch2, b) != hipSuccess) {
-        mv::set_error(MV_ERR_OUT_OF_MEMORY, "all-pairs scratch allocation of %zu bytes failed", b);
-        return MV_ERR_OUT_OF_MEMORY;
-    }
-    ctx->ap_scratch2_bytes = b;
-    return MV_OK;
-}
-void ap_swap_prepared(mv_context *ctx, int batch, int cap, const int *n1, const float *desc1) {
-    void *t = ctx->ap_scratch;
-    size_t tb = ctx->ap_scratch_bytes;
-    ctx->ap_scratch = ctx->ap_scratch2;
-    ctx->ap_scratch_bytes = ctx->ap_scratch2_bytes;
-    ctx->ap_scratch2 = t;
-    ctx->ap_scratch2_bytes = tb;
-    ctx->prep_batch = batch;
-    ctx->prep_cap = cap;
-    ctx->prep_n1 = n1;
-    ctx->prep_desc1 = desc1;
-    ctx->prep_staged = true;
-}
-}  // namespace
-
-extern "C" int mv_match_allpairs_f32_run_prepare_dev(mv_context *ctx, int batch, int cap, const int *n0,
-                                                     const int *n1, const float *desc0, const float *desc1,
-                                                     double thresh, int *match_idx, float *match_score,
-                                                     int next_batch, int next_cap, const int *next_n1,
-                                                     const float *next_desc1) {
-    MV_REQUIRE(ctx != nullptr && next_batch > 0 && next_cap > 0 && next_n1 && next_desc1);
-    if (!ctx->prep_desc1 || ctx->prep_batch != batch || ctx->prep_cap != cap || ctx->prep_n1 != n1 ||
-        ctx->prep_desc1 != desc1 || ctx->prep_screen != ctx->ap_screen) {
-        mv::set_error(MV_ERR_INVALID_ARG, "mv_match_allpairs_f32_run_prepare_dev: no matching prepare for this batch");
-        return MV_ERR_INVALID_ARG;
-    }
-    MV_HIP_TRY(hipSetDevice(ctx->device));
-    if (ctx->ap_screen == MV_SCREEN_I8) {  // one pass: nothing to stage for the next batch
-        const int st = ap_match(ctx, ctx->ap_screen, ctx->stream, nullptr, batch, cap, n0, n1, desc0, desc1, thresh,
-                                match_idx, match_score);
-        if (st != MV_OK) return st;
-        ctx->prep_batch = next_batch;
-        ctx->prep_cap = next_cap;
-        ctx->prep_n1 = next_n1;
-        ctx->prep_desc1 = next_desc1;
-        ctx->prep_staged = false;  // recorded, not staged (sequence mode needs a prepare)
-        return mv::set_status(MV_OK);
-    }
-    const int sc = ap_scratch2(ctx, mv::ap_image_bytes(ctx->ap_screen, next_batch, next_cap));
-    if (sc != MV_OK) return sc;
-    if (ctx->aux_stream) MV_HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_prep, 0));
-    int st;
-    if (ctx->ap_screen == MV_SCREEN_I8_STAGED) {
-        st = mv::launch_allpairs_q8_match_prepare(ctx->stream, ctx->ap_scratch, batch, cap, n0, n1, desc0, desc1,
-                                                  thresh, match_idx, match_score, 0, ctx->ap_scratch2, next_batch,
-                                                  next_cap, next_n1, next_desc1);
-    } else {  // the fp16 screen: the two kernels in stream order
-        st = ap_match(ctx, ctx->ap_screen, ctx->stream, ctx->ap_scratch, batch, cap, n0, n1, desc0, desc1, thresh,
-                      match_idx, match_score);
-        if (st == MV_OK)
-            st = ap_prepare(ctx->ap_screen, ctx->stream, ctx->ap_scratch2, next_batch, next_cap, next_n1, next_desc1);
-    }
-    if (st != MV_OK) return st;
-    ap_swap_prepared(ctx, next_batch, next_cap, next_n1, next_desc1);  // the next batch is now the prepared one
-    return mv::set_status(MV_OK);
-}
-
-namespace {
-// nn_match_two_way's keep (pairwise_pnp.py:307-313): dist < nn_thresh (float32 compare) and
-// the reverse argmin of the match is the row itself
-__global__ __launch_bounds__(256) void k_two_way_keep(long total, int cap, const int *__restrict__ n0v,
-                                                      const int *__restrict__ n1v, const int *__restrict__ ridx,
-                                                      float nn_thresh, int *__restrict__ fidx,
-                                                      float *__restrict__ fdist, int keep_dist) {
-    const long q = (long)blockIdx.x * 256 + threadIdx.x;
-    if (q >= total) return;
-    const long b = q / cap;
-    const int i = (int)(q % cap);
-    const int n0 = min(max(n0v[b], 0), cap), n1 = min(max(n1v[b], 0), cap);
-    const int j = fidx[q];
-    const bool keep = i < n0 && j >= 0 && j < n1 && fdist[q] < nn_thresh && ridx[b * cap + j] == i;
-    fidx[q] = keep ? j : -1;
-    if (keep_dist && !keep) fdist[q] = 0.f;
-}
-}  // namespace
-
-extern "C" int mv_match_two_way_f32_dev(mv_context *ctx, int batch, int cap, const int *n0, const int *n1,
-                                        const float *desc0, const float *desc1, double nn_thresh, int *match_idx,
-                                        float *match_dist) {
-    MV_REQUIRE(ctx != nullptr && batch > 0 && cap > 0 && n0 && n1 && desc0 && desc1 && match_idx);
-    if (!(nn_thresh >= 0.0)) {
-        mv::set_error(MV_ERR_INVALID_ARG, "nn_match_two_way: nn_thresh should be non-negative");
-        return MV_ERR_INVALID_ARG;
-    }
-    MV_HIP_TRY(hipSetDevice(ctx->device));
-    const int sc = ctx->ap_screen;
-    void *scr = nullptr;
-    if (sc != MV_SCREEN_I8) {  // the image screens stage each direction
-        scr = ap_scratch(ctx, mv::ap_image_bytes(ctx->ap_screen, batch, cap));
-        if (!scr) return MV_ERR_OUT_OF_MEMORY;
-        ctx->prep_desc1 = nullptr;  // the prepared image is overwritten
-        if (ctx->aux_stream) MV_HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_prep, 0));  // a staging in flight
-    }
-    const size_t nb = mv::align_up((size_t)batch * cap * 4, 256);
-    char *tmp = (char *)mv::scratch(ctx, 2 * nb);
-    if (!tmp) return MV_ERR_OUT_OF_MEMORY;
-    int *ridx = (int *)tmp;
-    float *fdist = match_dist ? match_dist : (float *)(tmp + nb);
-    hipStream_t s = ctx->stream;
-    // forward: rows of frame 0 against frame 1 (argmin distance + its exact distance)
-    int st = sc == MV_SCREEN_I8 ? MV_OK : ap_prepare(sc, s, scr, batch, cap, n1, desc1);
-    if (st == MV_OK) st = ap_match(ctx, sc, s, scr, batch, cap, n0, n1, desc0, desc1, 0.0, match_idx, fdist, 1);
-    // reverse: rows of frame 1 against frame 0 (indices only)
-    if (st == MV_OK && sc != MV_SCREEN_I8) st = ap_prepare(sc, s, scr, batch, cap, n0, desc0);
-    if (st == MV_OK) st = ap_match(ctx, sc, s, scr, batch, cap, n1, n0, desc1, desc0, 0.0, ridx, nullptr, 1);
-    if (st != MV_OK) return st;
-    const long total = (long)batch * cap;
-    hipLaunchKernelGGL(k_two_way_keep, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, total, cap, n0, n1,
-                       ridx, (float)nn_thresh, match_idx, fdist, match_dist ? 1 : 0);
-    MV_LAUNCH_CHECK();
-    return mv::set_status(MV_OK);
-}
-
-
-namespace {
-// Sequence mode on the default screen (cap <= 1024): k_q8t_match over the F - 1 pairs (frame b,
-// frame b + 1) addressed in place -- desc0 = desc, desc1 = desc + one frame, n0 = n, n1 = n + 1 -- a
-// whole pair per workgroup, each frame read once as frame 1 and once as frame 0 (the staged int8
-// images of k_q8_match<AI8> read 24 % fewer bytes but run the older, slower sweep: 4.0 ms per 8192
-// pairs against the one-pass kernel's 3.5)
-bool seq_one_pass(const mv_context *ctx, int cap) {
-    return ctx->ap_screen == MV_SCREEN_I8 && mv::allpairs_q8t_applies(cap, 0);
-}
-int seq_one_pass_run(mv_context *ctx, int frames, int cap, const int *n, const float *desc, double thresh,
-                     int *match_idx, float *match_score) {
-    void *fl = mv::scratch(ctx, mv::allpairs_q8t_scratch_bytes(frames - 1));
-    if (!fl) return MV_ERR_OUT_OF_MEMORY;
-    return mv::launch_allpairs_q8t_match(ctx->stream, fl, frames - 1, cap, n, n + 1, desc, desc + (size_t)cap * 256,
-                                         thresh, match_idx, match_score);
-}
-}  // namespace
-
-extern "C" int mv_match_sequence_f32_dev(mv_context *ctx, int frames, int cap, const int *n, const float *desc,
-                                         double thresh, int *match_idx, float *match_score) {
-    MV_REQUIRE(ctx != nullptr && frames >= 2 && cap > 0 && n && desc && match_idx);
-    if (ctx->ap_screen == MV_SCREEN_F16) {
-        mv::set_error(MV_ERR_INVALID_ARG, "mv_match_sequence_f32_dev: the int8 screens only");
-        return MV_ERR_INVALID_ARG;
-    }
-    MV_HIP_TRY(hipSetDevice(ctx->device));
-    if (seq_one_pass(ctx, cap)) {
-        const int st = seq_one_pass_run(ctx, frames, cap, n, desc, thresh, match_idx, match_score);
-        return st != MV_OK ? st : mv::set_status(MV_OK);
-    }
-    void *scr = ap_scratch(ctx, mv::ap_image_bytes(ctx->ap_screen, frames, cap));
-    if (!scr) return MV_ERR_OUT_OF_MEMORY;
-    ctx->prep_desc1 = nullptr;  // the prepared image is overwritten
-    if (ctx->aux_stream) MV_HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_prep, 0));  // a staging in flight
-    const int st = mv::launch_allpairs_q8_sequence(ctx->stream, scr, frames, cap, n, desc, thresh, match_idx,
-                                                   match_score);
-    return st != MV_OK ? st : mv::set_status(MV_OK);
-}
-
-extern "C" int mv_match_sequence_f32_run_prepare_dev(mv_context *ctx, int frames, int cap, const int *n,
-                                                     const float *desc, double thresh, int *match_idx,
-                                                     float *match_score, int next_frames, int next_cap,
-                                                     const int *next_n, const float *next_desc) {
-    MV_REQUIRE(ctx != nullptr && frames >= 2 && next_frames >= 2 && next_cap > 0 && next_n && next_desc);
-    if (ctx->ap_screen == MV_SCREEN_F16 || !ctx->prep_desc1 || ctx->prep_batch != frames ||
-        ctx->prep_cap != cap || ctx->prep_n1 != n || ctx->prep_desc1 != desc || ctx->prep_screen == MV_SCREEN_F16) {
-        mv::set_error(MV_ERR_INVALID_ARG,
-                      "mv_match_sequence_f32_run_prepare_dev: no matching prepare for these frames (int8 screen)");
-        return MV_ERR_INVALID_ARG;
-    }
-    MV_HIP_TRY(hipSetDevice(ctx->device));
-    if (seq_one_pass(ctx, cap)) {  // nothing staged: match this chunk in place, record the next one
-        const int st = seq_one_pass_run(ctx, frames, cap, n, desc, thresh, match_idx, match_score);
-        if (st != MV_OK) return st;
-        ctx->prep_batch = next_frames;
-        ctx->prep_cap = next_cap;
-        ctx->prep_n1 = next_n;
-        ctx->prep_desc1 = next_desc;
-        ctx->prep_staged = false;
-        return mv::set_status(MV_OK);
-    }
-    if (!ctx->prep_staged) {  // recorded by the one-pass screen's prepare: stage the images now
-        void *scr = ap_scratch(ctx, mv::ap_image_bytes(ctx->ap_screen, frames, cap));
-        if (!scr) return MV_ERR_OUT_OF_MEMORY;
-        if (ctx->aux_stream) MV_HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_prep, 0));
-        const int ps = ap_prepare(ctx->ap_screen, ctx->stream, scr, frames, cap, n, desc);
-        if (ps != MV_OK) return ps;
-        ctx->prep_staged = true;
-    }
-    const int sc = ap_scratch2(ctx, mv::ap_image_bytes(ctx->ap_screen, next_frames, next_cap));
-    if (sc != MV_OK) return sc;
-    if (ctx->aux_stream) MV_HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_prep, 0));
-    const int st = mv::launch_allpairs_q8_sequence(ctx->stream, ctx->ap_scratch, frames, cap, n, desc, thresh,
-                                                   match_idx, match_score, true, ctx->ap_scratch2, next_frames,
-                                                   next_cap, next_n, next_desc);
-    if (st != MV_OK) return st;
-    ap_swap_prepared(ctx, next_frames, next_cap, next_n, next_desc);
-    return mv::set_status(MV_OK);
-}

@@ -16,30 +16,17 @@
 #include <math.h>
 
 #include "mv_internal.hpp"
+#include "mv_wave.hpp"
 
 namespace {
 
 constexpr int KD = 256;
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ int xcd_remap(int b, int total) {
-    const int q = total / 8, r = total % 8, x = b % 8;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + b / 8;
-}
+using namespace wave;
 
 // |b|^2 of 4 rows per 16-lane row group: each load instruction reads 4 whole 256-B rows (1 KiB
 // contiguous per wave), 4 rows in flight per thread, the 16 partial sums reduced by ds_swizzle
 constexpr int NRM_U = 4;  // rows per thread
-__device__ __forceinline__ int swz_xor_i8(int v, int m) {
-    switch (m) {
-        case 1: return __builtin_amdgcn_ds_swizzle(v, (1 << 10) | 0x1F);
-        case 2: return __builtin_amdgcn_ds_swizzle(v, (2 << 10) | 0x1F);
-        case 4: return __builtin_amdgcn_ds_swizzle(v, (4 << 10) | 0x1F);
-        default: return __builtin_amdgcn_ds_swizzle(v, (8 << 10) | 0x1F);
-    }
-}
 __global__ __launch_bounds__(256) void k_i8_norms(long rows, const int8_t *__restrict__ d, int *__restrict__ nrm,
                                                   float *__restrict__ rnrm) {
     const int t = threadIdx.x, sub = t & 15;
@@ -56,10 +43,10 @@ __global__ __launch_bounds__(256) void k_i8_norms(long rows, const int8_t *__res
         s = __builtin_amdgcn_sdot4(x[u].y, x[u].y, s, false);
         s = __builtin_amdgcn_sdot4(x[u].z, x[u].z, s, false);
         s = __builtin_amdgcn_sdot4(x[u].w, x[u].w, s, false);
-        s += swz_xor_i8(s, 1);
-        s += swz_xor_i8(s, 2);
-        s += swz_xor_i8(s, 4);
-        s += swz_xor_i8(s, 8);
+        s += swz_xor<1>(s);
+        s += swz_xor<2>(s);
+        s += swz_xor<4>(s);
+        s += swz_xor<8>(s);
         const long r = base + 16 * u;
         if (sub == 0 && r < rows) {
             nrm[r] = s;
@@ -98,10 +85,10 @@ __global__ __launch_bounds__(256) void k_i8_prep(int batch, int cap, int cap64, 
         s = __builtin_amdgcn_sdot4(x[u].y, x[u].y, s, false);
         s = __builtin_amdgcn_sdot4(x[u].z, x[u].z, s, false);
         s = __builtin_amdgcn_sdot4(x[u].w, x[u].w, s, false);
-        s += swz_xor_i8(s, 1);
-        s += swz_xor_i8(s, 2);
-        s += swz_xor_i8(s, 4);
-        s += swz_xor_i8(s, 8);
+        s += swz_xor<1>(s);
+        s += swz_xor<2>(s);
+        s += swz_xor<4>(s);
+        s += swz_xor<8>(s);
         const float rb = s > 0 ? 1.0f / sqrtf((float)s) : 0.f;
         const float sc = 127.f * rb;
         const int w4[4] = {x[u].x, x[u].y, x[u].z, x[u].w};
@@ -170,45 +157,6 @@ constexpr int M_EPI = M_OFF_LM + M_BM * 4, M_RING = M_NBUF * M_SLOT;
 constexpr int M_OFF_NA = M_EPI > M_RING ? M_EPI : M_RING;  // [BM] i32 |a|^2
 constexpr int M_LDS = M_OFF_NA + M_BM * 4;
 static_assert(M_LDS <= 160 * 1024, "LDS");
-
-#pragma clang diagnostic ignored "-Winline-asm"
-template <int KOFF, int DOFF>
-__device__ __forceinline__ void glds16_i8(const void *sbase, unsigned voff, unsigned lds_byte) {
-    unsigned tmp;
-    asm volatile(
-        "v_add_u32 %0, %4, %1\n\t"
-        "s_add_u32 m0, %3, %5\n\t"
-        "global_load_lds_dwordx4 %0, %2"
-        : "=&v"(tmp)
-        : "v"(voff), "s"(sbase), "s"(lds_byte), "i"(KOFF), "i"(DOFF)
-        : "memory", "m0", "scc");
-}
-template <int DOFF>
-__device__ __forceinline__ void glds4_i8(const void *sbase, unsigned voff, unsigned lds_byte) {
-    asm volatile(
-        "s_add_u32 m0, %2, %3\n\t"
-        "global_load_lds_dword %0, %1"
-        :
-        : "v"(voff), "s"(sbase), "s"(lds_byte), "i"(DOFF)
-        : "memory", "m0", "scc");
-}
-template <int N>
-__device__ __forceinline__ void wait_vm_i8() {
-    __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));
-}
-// (f & keep) | tag in one instruction
-__device__ __forceinline__ float tag_i8(float f, unsigned keep, unsigned tag) {
-    float r;
-    asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(f), "v"(keep), "s"(tag));
-    return r;
-}
-// top-2 of {m1, m2, a, b} given m1 >= m2: m1' = max3(m1, a, b), m2' = max(m2, med3(m1, a, b))
-__device__ __forceinline__ void fold3_i8(float a, float b, float &m1, float &m2) {
-    float md;
-    asm("v_med3_f32 %0, %1, %2, %3" : "=v"(md) : "v"(m1), "v"(a), "v"(b));
-    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(m1) : "v"(m1), "v"(a), "v"(b));
-    asm("v_max_f32 %0, %1, %2" : "=v"(m2) : "v"(m2), "v"(md));
-}
 
 // two values of one row into its lane-local top-2 on integer keys (D << sh) | tag (sh: the tag
 // width, a VGPR; tags in SGPRs) -- one asm block, no hazard padding between its instructions
@@ -289,13 +237,13 @@ __device__ __forceinline__ void i8m_block(char *lds, int L, int tiles_r, int cap
     //   compiler's vmcnt waits drain the whole DMA ring
 #define I8_STAGE(SLOT)                                                                       \
     do {                                                                                     \
-        glds16_i8<0, (SLOT) * M_SLOT>(Bt, oB[0], dst_w);                                     \
-        glds16_i8<0, (SLOT) * M_SLOT + 4 * KD>(Bt, oB[1], dst_w);                            \
+        glds16_koff<0, (SLOT) * M_SLOT>(Bt, oB[0], dst_w);                                     \
+        glds16_koff<0, (SLOT) * M_SLOT + 4 * KD>(Bt, oB[1], dst_w);                            \
         if constexpr (M_DPW == 4) {                                                          \
-            glds16_i8<0, (SLOT) * M_SLOT + 8 * KD>(Bt, oB[M_DPW - 2], dst_w);                \
-            glds16_i8<0, (SLOT) * M_SLOT + 12 * KD>(Bt, oB[M_DPW - 1], dst_w);               \
+            glds16_koff<0, (SLOT) * M_SLOT + 8 * KD>(Bt, oB[M_DPW - 2], dst_w);                \
+            glds16_koff<0, (SLOT) * M_SLOT + 12 * KD>(Bt, oB[M_DPW - 1], dst_w);               \
         }                                                                                    \
-        glds4_i8<(SLOT) * M_SLOT + M_TILE>(rnb, oR, lds_base);                               \
+        glds4<(SLOT) * M_SLOT + M_TILE>(rnb, oR, lds_base);                               \
     } while (0)
 #define I8_OFFSETS(TC)                                                                       \
     do {                                                                                     \
@@ -380,7 +328,7 @@ __device__ __forceinline__ void i8m_block(char *lds, int L, int tiles_r, int cap
         _Pragma("unroll") for (int q = 2 * (S); q < 2 * (S) + 2; q++) {                      \
             const float a_ = __builtin_fmaf(__int_as_float(acc[FG][0][q]), (R0), (C0));      \
             const float b_ = __builtin_fmaf(__int_as_float(acc[FG][1][q]), (R1), (C1));      \
-            fold3_i8(tag_i8(a_, vkeep, (G0)), tag_i8(b_, vkeep, (G0) + 1u), m1[FG][q], m2[FG][q]); \
+            fold3(tag(a_, vkeep, (G0)), tag(b_, vkeep, (G0) + 1u), m1[FG][q], m2[FG][q]); \
         }                                                                                    \
     } while (0)
 #define I8_SEG(J, G, FG, G0, R0, R1, C0, C1)                                                 \
@@ -436,14 +384,14 @@ __device__ __forceinline__ void i8m_block(char *lds, int L, int tiles_r, int cap
         const unsigned gc_ = __builtin_amdgcn_readfirstlane(2u * (unsigned)tc);              \
         I8_SEG(J, 1, 0, gc_, pr0, pr1, pc0, pc1);                                            \
         if (ntile < ntc) {                                                                   \
-            wait_vm_i8<(M_DPW + 1) * (M_NBUF - 2)>();                                        \
+            wait_vm<(M_DPW + 1) * (M_NBUF - 2)>();                                        \
         } else {                                                                             \
-            wait_vm_i8<0>();                                                                 \
+            wait_vm<0>();                                                                 \
         }                                                                                    \
         __syncthreads();                                                                     \
     } while (0)
 
-    wait_vm_i8<0>();  // the prologue's tiles (issued before the A rows) and the A rows
+    wait_vm<0>();  // the prologue's tiles (issued before the A rows) and the A rows
     __syncthreads();
     for (int T = 0; T < ntc; T += 4) {
         I8_SLOT(0);
@@ -747,8 +695,8 @@ __global__ __launch_bounds__(IT_NT, 2) void k_i8t_match(int tiles_r, int cap, co
 #define IT_STAGE(TC, SLOT)                                                                   \
     do {                                                                                     \
         const unsigned o_ = (unsigned)((TC) * M_BN + dr) * KD + dcb;                         \
-        glds16_i8<0, (SLOT) * IT_TILE>(Bt, o_, dst_w);                                       \
-        glds16_i8<4 * KD, (SLOT) * IT_TILE + 4 * KD>(Bt, o_ ^ 64u, dst_w);                   \
+        glds16_koff<0, (SLOT) * IT_TILE>(Bt, o_, dst_w);                                       \
+        glds16_koff<4 * KD, (SLOT) * IT_TILE + 4 * KD>(Bt, o_ ^ 64u, dst_w);                   \
     } while (0)
     // prologue: tiles 0, 1, 2 before the A rows are read
     if (ntc > 0) IT_STAGE(0, 0);
@@ -830,7 +778,7 @@ __global__ __launch_bounds__(IT_NT, 2) void k_i8t_match(int tiles_r, int cap, co
         }                                                                                    \
     } while (0)
 
-    wait_vm_i8<0>();  // the prologue's tiles and the A rows
+    wait_vm<0>();  // the prologue's tiles and the A rows
     __syncthreads();
     i32x4 fq_[KD / 32];  // tile 0's block-0 fragments (later tiles': read during the tile before)
 #pragma unroll
@@ -863,11 +811,11 @@ __global__ __launch_bounds__(IT_NT, 2) void k_i8t_match(int tiles_r, int cap, co
         IT_UNIT(6, tg1);
         IT_UNIT(7, tg1);
         if (tc + 3 < ntc) {  // tile tc + 1 landed (tc + 2, tc + 3 may be in flight)
-            wait_vm_i8<2 * IT_DPW>();
+            wait_vm<2 * IT_DPW>();
         } else if (tc + 2 < ntc) {
-            wait_vm_i8<IT_DPW>();
+            wait_vm<IT_DPW>();
         } else {
-            wait_vm_i8<0>();
+            wait_vm<0>();
         }
         __syncthreads();
     }

@@ -10,6 +10,7 @@
 // with -ffp-contract=off and IEEE division.  Data are int8 and HBM/L2 bound:
 // no MFMA here (the window dot is 64..256 int8 MACs per candidate, v_dot4).
 #include "mv_internal.hpp"
+#include "mv_wave.hpp"
 
 
 namespace {
@@ -959,7 +960,7 @@ __global__ __launch_bounds__(256) void k_window_query(WinArgs a, int blocks_per_
 constexpr int kBandW = 5;
 constexpr int kBandList = 960;  // candidate-list capacity the eligibility test checks ((kBandW + 2r) * rows)
 
-typedef int i32x4_t __attribute__((ext_vector_type(4)));
+using i32x4_t = wave::i32x4;
 
 // One 16x16 tile's elements (lane: candidate column; rows 4 h + j): window membership, the
 // as-intended pass test 100 dot^2 > 81 |c|^2 |q|^2 and the exact running best.  The pass
@@ -1017,21 +1018,6 @@ constexpr int kWaveList = 512;     // candidate-list capacity per wave (more: se
 
 
 constexpr int kWinTileB = 16 * kDescD;  // one staged tile: 16 candidates x 256 B
-#pragma clang diagnostic ignored "-Winline-asm"  // m0 in the clobber list (as k_allpairs_i8.hip)
-// 64 lanes x 16 B from global (SGPR base + per-lane 32-bit offset) into LDS at M0 (wave-uniform)
-__device__ __forceinline__ void glds16_win(const void *sbase, unsigned voff, unsigned lds_byte) {
-    asm volatile(
-        "s_mov_b32 m0, %2\n\t"
-        "global_load_lds_dwordx4 %0, %1"
-        :
-        : "v"(voff), "s"(sbase), "s"(lds_byte)
-        : "memory", "m0");
-}
-template <int N>
-__device__ __forceinline__ void wait_vm_win() {
-    __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));
-}
-
 constexpr int WIN_WPE = 2;  // waves per EU the launch bound asks for (the kernel takes 126 VGPRs)
 __global__ __launch_bounds__(256, WIN_WPE) void k_window_wave(WinArgs a, int blocks_per_pair, int nblocks,
                                                      const unsigned long long *__restrict__ masks,
@@ -1137,7 +1123,7 @@ __global__ __launch_bounds__(256, WIN_WPE) void k_window_wave(WinArgs a, int blo
                     const int xy = lst[min(t * 16 + c, nc - 1)];
                     const unsigned voff =
                         (unsigned)(((xy >> 6) * R + (xy & 63)) * kDescD) + ((unsigned)((lane & 15) ^ c) << 4);
-                    glds16_win(d0, voff, dst + 1024u * k);
+                    wave::glds16_m0(d0, voff, dst + 1024u * k);
                 }
             };
             auto tile = [&](int nt) {
@@ -1169,9 +1155,9 @@ __global__ __launch_bounds__(256, WIN_WPE) void k_window_wave(WinArgs a, int blo
             if (ntiles > 1) stage(1);
             for (int nt = 0; nt < ntiles; nt++) {  // wave-uniform
                 if (nt + 1 < ntiles)
-                    wait_vm_win<4>();  // tile nt landed (tile nt + 1's 4 pieces may be in flight)
+                    wave::wait_vm<4>();  // tile nt landed (tile nt + 1's 4 pieces may be in flight)
                 else
-                    wait_vm_win<0>();
+                    wave::wait_vm<0>();
                 tile(nt);
             }
         }

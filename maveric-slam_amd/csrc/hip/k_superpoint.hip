@@ -25,6 +25,7 @@
 #include <math.h>
 
 #include "mv_internal.hpp"
+#include "mv_wave.hpp"
 #include "superpoint.h"
 
 struct mv_superpoint {
@@ -45,8 +46,8 @@ struct mv_superpoint {
 
 namespace {
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x16 __attribute__((ext_vector_type(16)));
+using wave::i32x4;
+using wave::i32x16;
 
 constexpr int SP_NT = 256;          // 4 waves
 
@@ -246,8 +247,8 @@ __global__ __launch_bounds__(SP_NT, CIN == 64 ? SP_OCC64 : 2) void k_sp_conv(con
         // on the f16 matrix cores: int8 taps and weights are exact in f16, every partial sum an
         // integer below 2^24 (exact in f32), the bias the C input -- the accumulator IS the
         // integer sum as a float, so the requantisation skips its int -> float conversion
-        typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-        typedef float f32x16 __attribute__((ext_vector_type(16)));
+        using h8 = wave::f16x8;
+        using wave::f32x16;
         h8 a1[2];
         f32x16 bias[2];
 #pragma unroll

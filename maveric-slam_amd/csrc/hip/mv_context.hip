@@ -98,40 +98,30 @@ static int retire_stream(mv_context *ctx, hipStream_t old) {
     return MV_OK;
 }
 
+int grow(mv_context *ctx, mv_buffer &b, size_t bytes, const char *what) {
+    if (bytes <= b.bytes) return MV_OK;
+    if (b.p) {
+        const int q = quiesce(ctx);  // the old buffer may be in use on any stream the context used
+        if (q != MV_OK) return q;
+        (void)hipFree(b.p);
+        b = mv_buffer{};
+    }
+    const size_t nb = align_up(bytes, 1 << 20);
+    if (hipMalloc(&b.p, nb) != hipSuccess) {
+        set_error(MV_ERR_OUT_OF_MEMORY, "%s allocation of %zu bytes failed", what, nb);
+        b.p = nullptr;
+        return MV_ERR_OUT_OF_MEMORY;
+    }
+    b.bytes = nb;
+    return MV_OK;
+}
+
 void *scratch(mv_context *ctx, size_t bytes) {
-    if (bytes <= ctx->scratch_bytes) return ctx->scratch;
-    if (ctx->scratch) {
-        (void)quiesce(ctx);  // the old buffer may be in use on any stream the context used
-        (void)hipFree(ctx->scratch);
-        ctx->scratch = nullptr;
-        ctx->scratch_bytes = 0;
-    }
-    size_t b = align_up(bytes, 1 << 20);
-    if (hipMalloc(&ctx->scratch, b) != hipSuccess) {
-        set_error(MV_ERR_OUT_OF_MEMORY, "scratch allocation of %zu bytes failed", b);
-        ctx->scratch = nullptr;
-        return nullptr;
-    }
-    ctx->scratch_bytes = b;
-    return ctx->scratch;
+    return grow(ctx, ctx->scratch, bytes, "scratch") == MV_OK ? ctx->scratch.p : nullptr;
 }
 
 void *stage(mv_context *ctx, size_t bytes) {
-    if (bytes <= ctx->stage_bytes) return ctx->stage_dev;
-    if (ctx->stage_dev) {
-        (void)quiesce(ctx);
-        (void)hipFree(ctx->stage_dev);
-        ctx->stage_dev = nullptr;
-        ctx->stage_bytes = 0;
-    }
-    size_t b = align_up(bytes, 1 << 20);
-    if (hipMalloc(&ctx->stage_dev, b) != hipSuccess) {
-        set_error(MV_ERR_OUT_OF_MEMORY, "staging allocation of %zu bytes failed", b);
-        ctx->stage_dev = nullptr;
-        return nullptr;
-    }
-    ctx->stage_bytes = b;
-    return ctx->stage_dev;
+    return grow(ctx, ctx->stage, bytes, "staging") == MV_OK ? ctx->stage.p : nullptr;
 }
 }  // namespace mv
 
@@ -207,10 +197,8 @@ int mv_context_destroy(mv_context *ctx) {
     }
     (void)hipStreamSynchronize(ctx->own_stream);  // the streams the context left (ev_retire)
     if (ctx->ev_retire) (void)hipEventDestroy(ctx->ev_retire);
-    if (ctx->scratch) (void)hipFree(ctx->scratch);
-    if (ctx->ap_scratch) (void)hipFree(ctx->ap_scratch);
-    if (ctx->ap_scratch2) (void)hipFree(ctx->ap_scratch2);
-    if (ctx->stage_dev) (void)hipFree(ctx->stage_dev);
+    for (const mv_buffer *b : {&ctx->scratch, &ctx->ap_image, &ctx->ap_image2, &ctx->stage})
+        if (b->p) (void)hipFree(b->p);
     if (ctx->i8_count_host) (void)hipHostFree(ctx->i8_count_host);
     (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
@@ -284,31 +272,14 @@ int mv_context_reserve(mv_context *ctx, int batch, int cap) {
     // image; the default one-pass int8 screen stages nothing (sequence mode allocates its images
     // on first use)
     const size_t img = ctx->ap_screen == MV_SCREEN_I8 ? 0 : mv::ap_image_bytes(ctx->ap_screen, batch, cap);
-    if (img && ctx->ap_scratch_bytes < img) {
-        if (ctx->ap_scratch) {
-            const int q = mv::quiesce(ctx);
-            if (q != MV_OK) return q;
-            MV_HIP_TRY(hipFree(ctx->ap_scratch));
-            ctx->ap_scratch = nullptr;
-            ctx->ap_scratch_bytes = 0;
-        }
-        ctx->prep_desc1 = nullptr;  // a prepared frame 1 lived in the freed buffer
-        const size_t ab = mv::align_up(img, 1 << 20);
-        if (hipMalloc(&ctx->ap_scratch, ab) != hipSuccess) return MV_ERR_OUT_OF_MEMORY;
-        ctx->ap_scratch_bytes = ab;
+    if (img > ctx->ap_image.bytes) {
+        const int st = mv::grow(ctx, ctx->ap_image, img, "all-pairs scratch");
+        // a prepared frame 1 lived in the old buffer (it survives only a failed quiesce)
+        if (st == MV_OK || !ctx->ap_image.p) ctx->prep.invalidate();
+        if (st != MV_OK) return st;
     }
-    if (img && ctx->ap_scratch2_bytes < img) {  // run_prepare's second image
-        if (ctx->ap_scratch2) {
-            const int q = mv::quiesce(ctx);
-            if (q != MV_OK) return q;
-            MV_HIP_TRY(hipFree(ctx->ap_scratch2));
-            ctx->ap_scratch2 = nullptr;
-            ctx->ap_scratch2_bytes = 0;
-        }
-        const size_t ab = mv::align_up(img, 1 << 20);
-        if (hipMalloc(&ctx->ap_scratch2, ab) != hipSuccess) return MV_ERR_OUT_OF_MEMORY;
-        ctx->ap_scratch2_bytes = ab;
-    }
+    const int st2 = mv::grow(ctx, ctx->ap_image2, img, "all-pairs scratch");  // run_prepare's second image
+    if (st2 != MV_OK) return st2;
     size_t need = mv::allpairs_i8_scratch_bytes(batch, cap);
     size_t b;
     b = mv::pose_scratch_bytes(batch, cap);

@@ -6,28 +6,42 @@
 
 #include "maveric_hip.h"
 
+// A grow-only device buffer of a context (mv::grow)
+struct mv_buffer {
+    void *p;
+    size_t bytes;
+};
+
+// The batch the last all-pairs prepare recorded: the run entry points check their arguments
+// against it.  desc1 == nullptr: nothing prepared.
+struct mv_prepared {
+    int batch, cap;
+    const int *n1;
+    const float *desc1;
+    int screen;   // the context's screen at the prepare
+    bool staged;  // frame 1 sits staged in ap_image (false: recorded only)
+    void record(int batch_, int cap_, const int *n1_, const float *desc1_, int screen_, bool staged_) {
+        batch = batch_, cap = cap_, n1 = n1_, desc1 = desc1_, screen = screen_, staged = staged_;
+    }
+    void invalidate() { desc1 = nullptr; }  // the image is overwritten or freed
+    bool matches(int batch_, int cap_, const int *n1_, const float *desc1_) const {
+        return desc1 && batch == batch_ && cap == cap_ && n1 == n1_ && desc1 == desc1_;
+    }
+};
+
 struct mv_context {
     int device;
     hipStream_t own_stream;
     hipStream_t stream;  // where every *_dev launch goes
-    void *scratch;       // device scratch, grown by mv_scratch()/mv_context_reserve()
-    size_t scratch_bytes;
-    // small host<->device staging for the single-pair host entry points
-    void *stage_dev;
-    size_t stage_bytes;
-    // all-pairs fp32: its own scratch (frame-1 fp16 image, norms, range flags) so that a
-    // prepare of the next batch on aux_stream never races the pose kernels on `stream`
-    void *ap_scratch;
-    size_t ap_scratch_bytes;
-    void *ap_scratch2;  // the other image of run_prepare (swapped with ap_scratch per call)
-    size_t ap_scratch2_bytes;
-    hipStream_t aux_stream;  // created on first prepare
+    mv_buffer scratch;   // device scratch, grown by mv::scratch() / mv_context_reserve()
+    mv_buffer stage;     // small host<->device staging for the single-pair host entry points
+    // all-pairs fp32 (mv_allpairs.hip): its own images (frame 1 as fp16 or int8, norms, range
+    // flags) so that a prepare of the next batch on aux_stream never races the pose kernels on
+    // `stream`; ap_image2 is the other image of run_prepare (swapped with ap_image per call)
+    mv_buffer ap_image, ap_image2;
+    hipStream_t aux_stream;  // created on first prepare, with ev_in and ev_prep
     hipEvent_t ev_in, ev_prep;
-    int prep_batch, prep_cap;  // what the last prepare staged (run checks it)
-    const int *prep_n1;
-    const float *prep_desc1;
-    int prep_screen;
-    bool prep_staged;  // the prepared batch's frame 1 sits staged in ap_scratch (false: recorded only)
+    mv_prepared prep;
     int ap_screen;  // mv_allpairs_screen of the fp32 all-pairs match (0 = int8, the default)
     // set_stream / use_own_stream away from a stream record this event on it and make own_stream
     // wait on it: own_stream then orders after all work issued on every stream the context left
@@ -48,7 +62,11 @@ int set_status(int status);
 
 // true while `s` is captured into a graph (or the query is refused: see mv_context.hip)
 int capture_state(hipStream_t s, bool *cap);  // MV_OK + *cap, or MV_ERR_HIP (reported)
-// Grow (never shrink) the context scratch; returns nullptr on failure.
+// Grow (never shrink) `b` to at least `bytes`, rounded up to 1 MiB.  Growing quiesces the context
+// and frees the old buffer; when the quiesce fails its status is returned and the old buffer stays.
+// A failed allocation leaves the buffer empty.  `what` names the buffer in the error message.
+int grow(mv_context *ctx, mv_buffer &b, size_t bytes, const char *what);
+// the context scratch / staging buffer of at least `bytes`; nullptr on failure
 void *scratch(mv_context *ctx, size_t bytes);
 void *stage(mv_context *ctx, size_t bytes);
 
@@ -59,7 +77,7 @@ inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 // a context buffer is freed; other contexts and threads are not blocked (no device-wide
 // synchronisation unless a synchronisation itself fails).
 int quiesce(mv_context *ctx);
-// bytes of one staged frame-1 image (ap_scratch / ap_scratch2) under `screen`
+// bytes of one staged frame-1 image (ap_image / ap_image2) under `screen` (mv_allpairs.hip)
 size_t ap_image_bytes(int screen, int batch, int cap);
 
 // Kernel profiler (mv_profile_* in maveric_hip.h): when enabled, launchers
@@ -108,7 +126,7 @@ int launch_softmax(hipStream_t s, int batch, int cells, const float *scales, con
                    int *max_idx, float *probs, int *num_valid);
 int launch_top_n_select(hipStream_t s, int batch, int cells, const int *max_idx, const float *probs, int N,
                         int cap, int *num_sel, int *patches, int *indices, float *sel_probs, int *status);
-size_t allpairs_f32_scratch_bytes(int batch, int cap);
+size_t allpairs_f32_image_bytes(int batch, int cap);  // the fp16 image of k_ap_split
 int launch_allpairs_f32_prepare(hipStream_t s, void *scratch, int batch, int cap, const int *n1,
                                 const float *desc1);
 int launch_allpairs_f32_match(hipStream_t s, void *scratch, int batch, int cap, const int *n0, const int *n1,

@@ -21,9 +21,14 @@
 #include <float.h>
 #include <math.h>
 
+#include "ap_exact.hpp"
 #include "mv_internal.hpp"
+#include "mv_wave.hpp"
 
 namespace q8 {
+
+using namespace wave;
+using namespace ap_exact;
 
 constexpr int KD = 256;
 constexpr int RG = 2;                      // 32-row groups per wave (64 rows)
@@ -38,68 +43,12 @@ constexpr float SCALE_LO = 9.094947017729282e-13f, SCALE_HI = 1099511627776.f;  
 template <int NW>
 constexpr int epi_bytes() { return NW * 32 * MT_STRIDE + NW * 64 * NCAND * 4 + NW * 64 * 4; }
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-
-// logical block -> a contiguous run of logical blocks per XCD (blocks b, b + 8 share one):
-// a pair's row blocks land on one XCD and share frame 1 through its L2
-__device__ __forceinline__ int xcd_remap(int b, int total) {
-    const int q = total / 8, r = total % 8, x = b % 8;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + b / 8;
-}
-
-#pragma clang diagnostic ignored "-Winline-asm"
-// LDS-DMA, 16 B per lane: LDS[m0 + 16 lane] <- global[sbase + voff] (the ring stays inline asm
-// with counted waits: the builtin makes the compiler drain vmcnt in front of every LDS read)
-template <int DOFF>
-__device__ __forceinline__ void glds16(const void *sbase, unsigned voff, unsigned lds_byte) {
-    asm volatile(
-        "s_add_u32 m0, %2, %3\n\t"
-        "global_load_lds_dwordx4 %0, %1"
-        :
-        : "v"(voff), "s"(sbase), "s"(lds_byte), "i"(DOFF)
-        : "memory", "m0", "scc");
-}
-template <int DOFF>
-__device__ __forceinline__ void glds4(const void *sbase, unsigned voff, unsigned lds_byte) {
-    asm volatile(
-        "s_add_u32 m0, %2, %3\n\t"
-        "global_load_lds_dword %0, %1"
-        :
-        : "v"(voff), "s"(sbase), "s"(lds_byte), "i"(DOFF)
-        : "memory", "m0", "scc");
-}
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));
-}
-// the tagged top-2 fold: m1' = max3(m1, a, b), m2' = max(m2, med3(m1, a, b))
-__device__ __forceinline__ void fold3(float a, float b, float &m1, float &m2) {
-    float md;
-    asm("v_med3_f32 %0, %1, %2, %3" : "=v"(md) : "v"(m1), "v"(a), "v"(b));
-    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(m1) : "v"(m1), "v"(a), "v"(b));
-    asm("v_max_f32 %0, %1, %2" : "=v"(m2) : "v"(m2), "v"(md));
-}
-__device__ __forceinline__ float tag(float f, unsigned keep, unsigned tg) {
-    float r;
-    asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(f), "v"(keep), "s"(tg));
-    return r;
-}
 // max(m, |a|, |b|) in one instruction (maxNum: a NaN operand is dropped -- callers catch NaN
 // through a sum of squares, which propagates it)
 __device__ __forceinline__ float absmax3(float m, float a, float b) {
     float r;
     asm("v_max3_f32 %0, %1, |%2|, |%3|" : "=v"(r) : "v"(m), "v"(a), "v"(b));
     return r;
-}
-template <int M>
-__device__ __forceinline__ float swz_xor(float v) {
-    return __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), (M << 10) | 0x1F));
-}
-template <int M>
-__device__ __forceinline__ int swz_xor(int v) {
-    return __builtin_amdgcn_ds_swizzle(v, (M << 10) | 0x1F);
 }
 // D = 0x40800000 (the bits of 4.0) + A.B: the first k32 step of a chain, C as the inline
 // constant 4.0 (a builtin with a constant C operand gets it hoisted into 16 VGPRs).  The
@@ -121,29 +70,6 @@ __device__ __forceinline__ int pack4(float x0, float x1, float x2, float x3, flo
     return (int)__builtin_amdgcn_perm(p23, p01, 0x05040100u);
 }
 
-// The reference's sequential fp32 dot (mul then add, k = 0..255), 4 load batches per operand.
-__device__ __forceinline__ float exact_dot(const float *__restrict__ a, const float *__restrict__ b) {
-    constexpr int U = 16;
-    float s = 0.f;
-#pragma unroll
-    for (int bt = 0; bt < KD / (4 * U); bt++) {
-        float4 xa[U], xb[U];
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            xa[u] = *reinterpret_cast<const float4 *>(a + 4 * U * bt + 4 * u);
-            xb[u] = *reinterpret_cast<const float4 *>(b + 4 * U * bt + 4 * u);
-        }
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const float4 x = xa[u], y = xb[u];
-            s = __fadd_rn(s, __fmul_rn(x.x, y.x));
-            s = __fadd_rn(s, __fmul_rn(x.y, y.y));
-            s = __fadd_rn(s, __fmul_rn(x.z, y.z));
-            s = __fadd_rn(s, __fmul_rn(x.w, y.w));
-        }
-    }
-    return s;
-}
 // The deferred maximiser re-scores load their rows COOPERATIVELY (coop_exact_dots) with
 // Q8_COOP_PD 16-float chunks in flight.  Why: exact_dot's per-lane loads put 64 different rows
 // (64 cache lines) under every load instruction, so a wave's re-scores cost ~38 x 128 line
@@ -228,18 +154,6 @@ __device__ __forceinline__ float coop_exact_dots(const float *__restrict__ A, co
         __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): this chunk's reads done before the next writes
     }
     return bcol >= 0 ? s : 0.f;
-}
-// nn_match_two_way's distance (pairwise_pnp.py:303): sqrt(2 - 2 clip(dot, -1, 1)) in float32
-__device__ __forceinline__ float dist(float e) {
-    const float c = e != e ? e : fminf(fmaxf(e, -1.f), 1.f);
-    return sqrtf(__fsub_rn(2.f, __fmul_rn(2.f, c)));
-}
-// dmode 0: larger dot, ties to the smaller index (NaN never wins); dmode 1: np.argmin
-__device__ __forceinline__ bool better(int dmode, float v, int j, float bv, int bj) {
-    if (!dmode) return v > bv || (v == bv && j < bj);
-    const bool nv = v != v, nb = bv != bv;
-    if (nv || nb) return nv && (!nb || j < bj);
-    return v < bv || (v == bv && j < bj);
 }
 
 // ---- the A phase: the wave's 2 x 32 frame-0 rows (rbase + 32 g + i of the block), fp32 ->
@@ -489,7 +403,7 @@ __device__ __forceinline__ void epilogue(char *epi, const float2 *rowv, float (&
         const bool full = flagged || rv.y < 0.f;
         const float *arow = A + (size_t)(row0 + rl) * KD;
         float bs = dmode ? __builtin_inff() : -__builtin_inff();
-        int bj = 0x7fffffff, need = -1;
+        int bj = NO_COLUMN, need = -1;
         bool wide = live && full;
         if (wide && fh == 0) lmask[rl] = 0xffffffffu;
         if (live && !full) {
@@ -618,7 +532,7 @@ __device__ __forceinline__ void epilogue(char *epi, const float2 *rowv, float (&
             const int rl = w * 64 + g * 32 + fr;
             const float bs = bs_g[g];
             const int bj = bj_g[g];
-            const bool keep = bj != 0x7fffffff && (dmode || ((double)bs > thresh && bs > 0.f));
+            const bool keep = bj != NO_COLUMN && (dmode || ((double)bs > thresh && bs > 0.f));
             oidx[rl] = keep ? bj : -1;
             if (oscore) oscore[rl] = keep ? bs : 0.f;
         }
@@ -631,7 +545,7 @@ __device__ __forceinline__ void epilogue(char *epi, const float2 *rowv, float (&
             const int r = w * 64 + g * 32 + __builtin_ctz(dm);
             const float *a = A + (size_t)(row0 + r) * KD;
             float ws = dmode ? __builtin_inff() : -__builtin_inff();
-            int wj = 0x7fffffff;
+            int wj = NO_COLUMN;
             for (unsigned Lm = lmask[r]; Lm; Lm &= Lm - 1) {
                 const int f = __builtin_ctz(Lm);
                 for (int j = f + 32 * lane; j < n1; j += 32 * 64) {
@@ -662,7 +576,7 @@ __device__ __forceinline__ void epilogue(char *epi, const float2 *rowv, float (&
             Q8_WRED(32);
 #undef Q8_WRED
             if (lane == 0) {
-                const bool keep = wj != 0x7fffffff && (dmode || ((double)ws > thresh && ws > 0.f));
+                const bool keep = wj != NO_COLUMN && (dmode || ((double)ws > thresh && ws > 0.f));
                 oidx[r] = keep ? wj : -1;
                 if (oscore) oscore[r] = keep ? ws : 0.f;
             }

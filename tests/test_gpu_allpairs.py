@@ -518,6 +518,89 @@ def test_prepare_then_one_shot_calls(ctx, screen, orc, torch_cuda):
         ctx.set_stream(None)
 
 
+def _small_batch(torch, seeds, ns):
+    """one pair per seed, n0 = n1 = ns[k], cap 64: the pairs and their device batch"""
+    pairs = []
+    for s, n in zip(seeds, ns):
+        p = synth.synth_pair_f32(s, n=n)
+        pairs.append((p["desc0"], p["desc1"]))
+    return pairs, _batch_f32(torch, pairs, 64)
+
+
+def _assert_batch_equals_oracle(orc, pairs, idx, sc):
+    idx, sc = idx.cpu().numpy(), sc.cpu().numpy()
+    for q, (a, c) in enumerate(pairs):
+        i2, s2 = orc.allpairs_f32(a, c, 0.8)
+        assert (idx[q, :a.shape[0]] == i2).all(), q
+        assert (bits(sc[q, :a.shape[0]]) == bits(s2)).all(), q
+        assert (idx[q, a.shape[0]:] == -1).all(), q
+
+
+@pytest.mark.parametrize("a,b", [("i8", "i8s"), ("i8s", "f16"), ("f16", "i8")])
+def test_prepare_does_not_survive_screen_switch(ctx, orc, torch_cuda, a, b):
+    """a batch prepared under screen a is refused under screen b before anything is launched (the
+    outputs keep their sentinel), and runs once the context is back on a"""
+    import mvtrack
+
+    torch = torch_cuda
+    pairs, (D0, D1, N0, N1) = _small_batch(torch, (1201, 1202), (64, 37))
+    idx = torch.full((2, 64), -7, dtype=torch.int32, device=D0.device)
+    sc = torch.full((2, 64), -7.0, dtype=torch.float32, device=D0.device)
+    ctx.set_stream(torch.cuda.current_stream())
+    try:
+        ctx.set_allpairs_screen(a)
+        ctx.match_allpairs_f32_prepare(D1, N1)
+        ctx.set_allpairs_screen(b)
+        with pytest.raises(RuntimeError):
+            ctx.match_allpairs_f32_run(D0, D1, N0, N1, idx, sc, 0.8)
+        assert mvtrack.lib().mv_last_status() == mvtrack.MV_ERR_INVALID_ARG
+        torch.cuda.synchronize()
+        assert (idx == -7).all() and (sc == -7.0).all()
+        ctx.set_allpairs_screen(a)
+        ctx.match_allpairs_f32_run(D0, D1, N0, N1, idx, sc, 0.8)
+        torch.cuda.synchronize()
+        _assert_batch_equals_oracle(orc, pairs, idx, sc)
+    finally:
+        ctx.set_allpairs_screen("i8")
+        ctx.set_stream(None)
+
+
+@pytest.mark.parametrize("scr", ["i8", "i8s", "f16"])
+def test_reserve_between_prepare_and_run(orc, torch_cuda, scr):
+    """reserve(64, 1024) after a prepare of one 64-row pair on a context of its own: the staged
+    screens' image outgrows the 1 MiB the prepare allocated, so the prepared image is freed and the
+    run refused; the default screen staged nothing and runs.  A new prepare then runs on every
+    screen."""
+    import mvtrack
+
+    torch = torch_cuda
+    pairs, (D0, D1, N0, N1) = _small_batch(torch, (1211,), (64,))
+    idx = torch.full((1, 64), -7, dtype=torch.int32, device=D0.device)
+    sc = torch.full((1, 64), -7.0, dtype=torch.float32, device=D0.device)
+    c = mvtrack.Context(0)
+    try:
+        c.set_allpairs_screen(scr)
+        c.set_stream(torch.cuda.current_stream())
+        c.match_allpairs_f32_prepare(D1, N1)
+        c.reserve(64, 1024)
+        if scr == "i8":
+            c.match_allpairs_f32_run(D0, D1, N0, N1, idx, sc, 0.8)
+            torch.cuda.synchronize()
+            _assert_batch_equals_oracle(orc, pairs, idx, sc)
+        else:
+            with pytest.raises(RuntimeError):
+                c.match_allpairs_f32_run(D0, D1, N0, N1, idx, sc, 0.8)
+            assert mvtrack.lib().mv_last_status() == mvtrack.MV_ERR_INVALID_ARG
+        idx.fill_(-7)
+        sc.fill_(-7.0)
+        c.match_allpairs_f32_prepare(D1, N1)
+        c.match_allpairs_f32_run(D0, D1, N0, N1, idx, sc, 0.8)
+        torch.cuda.synchronize()
+        _assert_batch_equals_oracle(orc, pairs, idx, sc)
+    finally:
+        c.close()
+
+
 @pytest.mark.parametrize("n1", [4096, 4097, 8192, 8193])
 def test_allpairs_f32_long_frame1(ctx, screen, orc, torch_cuda, n1):
     """frame 1 beyond 4096 keypoints: the one-pass kernel leaves the integer keys (7-bit tags hold

@@ -181,6 +181,61 @@ def test_sequence_run_prepare_chain(ctx, orc, torch_cuda, seq_screen):
         ctx.set_stream(None)
 
 
+def test_sequence_chunks_above_one_pass_cap(orc, torch_cuda):
+    """cap = 1025 on the default screen: the smallest cap the one-pass kernel does not take (and a
+    one-row ragged column tile).  The prepare only records chunk 0; the first run_prepare stages it
+    on first use into a freshly allocated image (a context of its own), the chain goes on through the
+    staged int8 kernels and ends in a one-shot call, which overwrites the prepared image: a
+    run_prepare after it is refused.  Every pair equals the oracle."""
+    import mvtrack
+
+    torch = torch_cuda
+    dev = torch.device("cuda:0")
+    rng = np.random.default_rng(31)
+    cap = 1025
+    chunks = []
+    for ns in ([1025, 1025, 0], [int(rng.integers(1, cap + 1)), int(rng.integers(1, cap + 1))],
+               [int(rng.integers(1, cap + 1)), 1, 1025]):
+        D = _track(rng, len(ns), cap, ns)
+        chunks.append((D, ns, torch.from_numpy(D).to(dev), torch.from_numpy(np.asarray(ns, np.int32)).to(dev)))
+    c = mvtrack.Context(0)
+    try:
+        c.set_allpairs_screen("i8")
+        c.set_stream(torch.cuda.current_stream())
+        c.match_allpairs_f32_prepare(chunks[0][2], chunks[0][3])  # records only
+        for k, (D, ns, d, n) in enumerate(chunks):
+            F = D.shape[0]
+            scores = k != 1
+            idx = torch.full((F - 1, cap), -7, dtype=torch.int32, device=dev)
+            sc = torch.full((F - 1, cap), 7.0, dtype=torch.float32, device=dev) if scores else None
+            if k + 1 < len(chunks):
+                c.match_sequence_f32_run_prepare(d, n, idx, sc, chunks[k + 1][2], chunks[k + 1][3])
+            else:
+                c.match_sequence_f32(d, n, idx, sc)
+            torch.cuda.synchronize()
+            idx = idx.cpu().numpy()
+            sc = sc.cpu().numpy() if scores else None
+            for b in range(F - 1):
+                n0, n1 = ns[b], ns[b + 1]
+                assert (idx[b, n0:] == -1).all(), (k, b)
+                if n0 == 0:
+                    continue
+                if n1 == 0:
+                    assert (idx[b, :n0] == -1).all(), (k, b)
+                    continue
+                i2, s2 = orc.allpairs_f32(D[b, :n0], D[b + 1, :n1], 0.8)
+                assert (idx[b, :n0] == i2).all(), (k, b)
+                if scores:
+                    assert (_bits(sc[b, :n0]) == _bits(s2)).all(), (k, b)
+        D, ns, d, n = chunks[2]
+        with pytest.raises(RuntimeError):  # the staged one-shot call invalidated the image
+            c.match_sequence_f32_run_prepare(d, n, torch.empty((2, cap), dtype=torch.int32, device=dev), None, d, n)
+        assert mvtrack.lib().mv_last_status() == mvtrack.MV_ERR_INVALID_ARG
+        torch.cuda.synchronize()
+    finally:
+        c.close()
+
+
 def test_sequence_track_end_to_end(ctx, orc, torch_cuda):
     """A camera moving by the 785 -> 786 transform per frame through a 3-D scene: each frame
     re-observes the previous frame's points still in view (60 % of its rows) and adds fresh
