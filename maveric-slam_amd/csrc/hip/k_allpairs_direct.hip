@@ -82,26 +82,6 @@ __device__ unsigned long long g_d_trace[D_TRACE_BLOCKS * D_NW * 10];
 #define D_SYNC() __syncthreads()
 #endif
 
-// max |b| and sum |b|^2 over a row's 16 lanes (quad_perm [1,0,3,2], [2,3,0,1],
-// row_half_mirror, row_mirror), the two reductions interleaved so that every DPP read is two
-// instructions behind the write it reads (no NaN canonicalisation in the max: NaN is caught by
-// |b|^2); every lane of the 16 ends with the same values
-__device__ __forceinline__ void row16_max_sum(float &m, float &q2) {
-    asm("s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %1, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 0\n\t"
-        "v_max_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %1, %1, %1 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 0\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %1, %1, %1 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 0\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_mirror row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %1, %1, %1 row_mirror row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1"
-        : "+v"(m), "+v"(q2));
-}
 // two values of one row folded into its lane-local top-2 on integer keys (held in float
 // registers' bits): the keys (d << sh) | tag by v_lshl_or_b32 (shift per lane in a VGPR, tag in
 // an SGPR), m1' = max3(m1, ka, kb), m2' = max(m2, med3(m1, ka, kb)) -- one asm block, so that
@@ -595,14 +575,18 @@ __global__ __launch_bounds__(D_NT, 2) void k_q8d_handback(int tiles_r, int cap, 
                                                           int *__restrict__ match_idx, float *__restrict__ match_score,
                                                           const int *__restrict__ only, int nblocks) {
     __shared__ __attribute__((aligned(16))) char lds[D_LDS];
-    // the flag scan first, in scalar registers: a workgroup with nothing handed back leaves before
-    // any of the (spilling) float-path code runs
-    int L = blockIdx.x;
-    while (L < nblocks && !__builtin_amdgcn_readfirstlane(only[L / tiles_r])) L += gridDim.x;
-    for (; L < nblocks; L += gridDim.x) {
-        if (!__builtin_amdgcn_readfirstlane(only[L / tiles_r])) continue;  // uniform: one flag per block
-        q8d_block(lds, L, tiles_r, cap, n0v, n1v, desc0, desc1, thresh, 0, match_idx, match_score);
-        __syncthreads();  // the next row block reuses the LDS
+    // the flag scan first: lane l of every wave loads the flag of the workgroup's l-th row block
+    // (blockIdx.x + l gridDim.x, + 64 gridDim.x per round) and a ballot gives all 64 answers in one
+    // round trip -- the same mask in every wave, so the walk over its bits is uniform.  A workgroup
+    // with nothing handed back leaves before any of the (spilling) float-path code runs.
+    for (long base = blockIdx.x; base < nblocks; base += 64l * gridDim.x) {
+        const long Ll = base + (long)(threadIdx.x & 63) * gridDim.x;
+        const int f = Ll < nblocks ? only[Ll / tiles_r] : 0;
+        for (unsigned long long m = __ballot(f != 0); m; m &= m - 1) {
+            const int L = (int)(base + (long)__builtin_ctzll(m) * gridDim.x);
+            q8d_block(lds, L, tiles_r, cap, n0v, n1v, desc0, desc1, thresh, 0, match_idx, match_score);
+            __syncthreads();  // the next row block reuses the LDS
+        }
     }
 }
 
@@ -629,7 +613,8 @@ constexpr int T_BM = 32 * T_RG * D_NW;              // 1024 rows: the whole pair
 constexpr int T_OFF_ROW = D_OFF_RING + 2 * D_SLOT;  // [T_BM] float2 (|a|^2, s_a)
 constexpr int T_OFF_MISC = T_OFF_ROW + T_BM * 8;    // [NW][4] per-wave statistics
 constexpr int T_OFF_COL = T_OFF_MISC + D_NW * 16;   // each frame-1 column's key shift (1 B)
-constexpr int T_LDS = T_OFF_COL + T_BM;
+constexpr int T_OFF_TKT = T_OFF_COL + T_BM;         // the workgroup's next pair (one word)
+constexpr int T_LDS = T_OFF_TKT + 16;
 constexpr int T_EPI_MASK = D_NW * 8192;             // epilogue: [NW] 8-KiB re-score buffers, [T_BM] wide masks
 static_assert(T_EPI_MASK + T_BM * 4 <= T_OFF_ROW, "the epilogue fits staging + ring");
 constexpr unsigned T_RESCAN = 0x80000000u;  // wide-mask bit: the row is left to k_q8t_rescan
@@ -990,71 +975,120 @@ __device__ __forceinline__ unsigned epilogue_t(char *epi, const float2 *rowv, co
     return nwide << 16 | nneed;
 }
 
-__global__ __launch_bounds__(D_NT, 2) void k_q8t_match(int cap, const int *__restrict__ n0v,
+// Persistent: min(batch, CU count) workgroups, each a loop over pairs.  The first pair of a workgroup
+// is its block index; every further one is a ticket drawn from `ticket` (a device word of the
+// context, 0 at launch; k_q8t_rescan, next in the stream, zeroes it again), so a workgroup that
+// starts late -- its CU still busy with another context's pose kernel -- simply takes fewer pairs.
+// The ticket is drawn at the top of an iteration and handed to the workgroup through LDS behind the
+// barrier after the A phase.  Every exit from an iteration is uniform over the workgroup and ends
+// at the barrier that closes the iteration (the next pair's DMA and A images overwrite the LDS the
+// epilogue reads); the sweep returns with every DMA drained.  Each pair's flags are zeroed here,
+// by the thread that may set `fallback` and ahead of the barriers that precede any wave's
+// `rs_flags` store: no memset per launch, and flags past `batch` are never read.
+__global__ __launch_bounds__(D_NT, 2) void k_q8t_match(int batch, int cap, const int *__restrict__ n0v,
                                                        const int *__restrict__ n1v, const float *__restrict__ desc0,
-                                                       const float *__restrict__ desc1, double thresh,
+                                                       const float *__restrict__ desc1, double thresh_,
                                                        int *__restrict__ match_idx, float *__restrict__ match_score,
                                                        int *__restrict__ fallback, int *__restrict__ rs_flags,
-                                                       unsigned char *__restrict__ rs_colsh) {
+                                                       unsigned char *__restrict__ rs_colsh, int *__restrict__ ticket) {
     __shared__ __attribute__((aligned(16))) char lds[T_LDS];
-#ifdef MV_TRACE
-    unsigned long long ts_[10] = {};
-    D_STAMP(0);
-#endif
-    const int pair = blockIdx.x;
-    const int n0 = min(max(n0v[pair], 0), cap), n1 = min(max(n1v[pair], 0), cap);
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    int *oidx = match_idx + (size_t)pair * cap;
-    float *oscore = match_score ? match_score + (size_t)pair * cap : nullptr;  // null: indices only
-    for (int r = t; r < cap; r += D_NT)
-        if (r >= n0 || n1 <= 0) {  // rows in [n0, cap): no match
-            oidx[r] = -1;
-            if (oscore) oscore[r] = 0.f;
-        }
-    if (n0 <= 0 || n1 <= 0) return;
-    const float *A = desc0 + (size_t)pair * cap * KD;
-    const float *B = desc1 + (size_t)pair * cap * KD;
-    const int ntc = (n1 + BN - 1) / BN;
-    const int wu = __builtin_amdgcn_readfirstlane(w);
-    const unsigned chunk16 = (unsigned)(4 * (lane & 15) + (lane >> 4)) * 16;
     const unsigned lds_base = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char *)lds;
     float2 *rowv = reinterpret_cast<float2 *>(lds + T_OFF_ROW);
     float *misc = reinterpret_cast<float *>(lds + T_OFF_MISC);
-    // ---- prologue: halves 0, 1 in flight beside the A phase (128 rows per wave) ----
-    dma_half(B, 0, n1, wu, chunk16, lds_base);
-    dma_half(B, 1, n1, wu, chunk16, lds_base + D_HALF);
-    i32x4 aI[T_RG][KD / 32];
-    // the A rows' loads software-pipelined (batch b + 1 issued before batch b is quantised): 3.504-3.514
-    // against 3.527-3.541 ms per launch, same box, ABAB (profiles/r06d_apipe_ab.log)
-    a_phase_pipe<D_QB, T_RG>(lds + D_OFF_AIMG + w * 32 * KD, rowv, w * (32 * T_RG), 0, n0, lane, A, aI);
-    D_STAMP(1);
-    __syncthreads();  // the A images (staging slot 2 + the ring) are consumed
-    float m1[T_RG], m2[T_RG];
-    const int tb = 32 - __builtin_clz(32 * ntc - 1);  // tags (2 tc + jb) 16 + r < 32 ntc
-    const Sweep st = block_stats(sweep_t(lds, B, n1, t, lane, wu, chunk16, lds_base, aI, m1, m2, tb), misc, w, lane);
-    D_STAMP(2);
-    if (st.bad || !(st.b2max <= T_B2MAX)) {  // outside the keys' range: k_q8d_match redoes the pair
-        if (t == 0) fallback[pair] = 1;
-        return;
-    }
-    const double Bn = sqrt((double)st.b2max) * 1.0001;
-    const double Eb = 8.0001 * (double)st.smax + 1e-30;
-    const unsigned ecnt = epilogue_t(lds, rowv, m1, m2, Bn, Eb, tb, w, lane, n0, n1, A, B, oidx, oscore, thresh,
-                                     reinterpret_cast<const unsigned char *>(lds + T_OFF_COL), rs_flags + pair,
-                                     rs_colsh + (size_t)pair * T_BM);
-    (void)ecnt;
+    int *tkt = reinterpret_cast<int *>(lds + T_OFF_TKT);
+    const int wu = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    for (int pair_ = blockIdx.x;;) {
+        const int pair = __builtin_amdgcn_readfirstlane(pair_);  // the same in every thread: scalar
+        if (pair >= batch) break;
+        // the thread index rebuilt per iteration from the wave's number (a scalar register) and made
+        // opaque: neither it nor anything derived from it (the phases' lane addresses) or from the
+        // threshold is hoisted out of the loop to sit in vector registers across the sweep
+        int t;
+        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0\n\tv_lshl_add_u32 %0, %1, 6, %0"
+                     : "=&v"(t)
+                     : "s"(wu));
+        __builtin_assume(t >= 0 && t < D_NT);
+        int th_lo = __double2loint(thresh_), th_hi = __double2hiint(thresh_);
+        asm volatile("" : "+s"(th_lo), "+s"(th_hi));
+        const double thresh = __hiloint2double(th_hi, th_lo);
+        const int lane = t & 63, w = t >> 6;
+        const unsigned chunk16 = (unsigned)(4 * (lane & 15) + (lane >> 4)) * 16;
 #ifdef MV_TRACE
-    D_STAMP(3);
-    ts_[8] = ecnt;
-    if (lane == 0 && blockIdx.x < D_TRACE_BLOCKS) {
-        unsigned long long *o = g_d_trace + ((size_t)blockIdx.x * D_NW + w) * 10;
-        for (int k = 0; k < 6; k++) o[k] = ts_[k];  // memtime x 4, memrealtime at entry / after A
-        o[6] = __smid();
-        o[7] = __builtin_amdgcn_s_memrealtime();
-        o[8] = ts_[8];
-        o[9] = ts_[9];
-    }
+        unsigned long long ts_[10] = {};
+        D_STAMP(0);
 #endif
+        int nxt = 0;
+        if (t == 0) {
+            nxt = (int)gridDim.x + atomicAdd(ticket, 1);
+            fallback[pair] = 0;
+            rs_flags[pair] = 0;
+        }
+        // (loads inside a loop that stores are vector loads: the counts back into scalar registers)
+        const int n0 = __builtin_amdgcn_readfirstlane(min(max(n0v[pair], 0), cap));
+        const int n1 = __builtin_amdgcn_readfirstlane(min(max(n1v[pair], 0), cap));
+        int *oidx = match_idx + (size_t)pair * cap;
+        float *oscore = match_score ? match_score + (size_t)pair * cap : nullptr;  // null: indices only
+        for (int r = t; r < cap; r += D_NT)
+            if (r >= n0 || n1 <= 0) {  // rows in [n0, cap): no match
+                oidx[r] = -1;
+                if (oscore) oscore[r] = 0.f;
+            }
+        if (n0 <= 0 || n1 <= 0) {  // nothing in flight, no LDS touched but the ticket
+            if (t == 0) *tkt = nxt;
+            __syncthreads();
+            pair_ = *tkt;
+            __syncthreads();  // the ticket is read before the next iteration may write it
+            continue;
+        }
+        const float *A = desc0 + (size_t)pair * cap * KD;
+        // (the DMA's base must sit in scalar registers whatever the register pressure)
+        const uintptr_t b_ = (uintptr_t)(desc1 + (size_t)pair * cap * KD);
+        const float *B = reinterpret_cast<const float *>(
+            (uintptr_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)b_) |
+            (uintptr_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(b_ >> 32)) << 32);
+        const int ntc = (n1 + BN - 1) / BN;
+        // ---- prologue: halves 0, 1 in flight beside the A phase (128 rows per wave) ----
+        dma_half(B, 0, n1, wu, chunk16, lds_base);
+        dma_half(B, 1, n1, wu, chunk16, lds_base + D_HALF);
+        i32x4 aI[T_RG][KD / 32];
+        // the A rows' loads software-pipelined (batch b + 1 issued before batch b is quantised): 3.504-3.514
+        // against 3.527-3.541 ms per launch, same box, ABAB (profiles/r06d_apipe_ab.log)
+        a_phase_pipe<D_QB, T_RG>(lds + D_OFF_AIMG + w * 32 * KD, rowv, w * (32 * T_RG), 0, n0, lane, A, aI);
+        D_STAMP(1);
+        if (t == 0) *tkt = nxt;
+        __syncthreads();  // the A images (staging slot 2 + the ring) are consumed; the ticket is in LDS
+        const int pair_next = __builtin_amdgcn_readfirstlane(*tkt);  // in a scalar register over the sweep
+        float m1[T_RG], m2[T_RG];
+        const int tb = 32 - __builtin_clz(32 * ntc - 1);  // tags (2 tc + jb) 16 + r < 32 ntc
+        const Sweep st =
+            block_stats(sweep_t(lds, B, n1, t, lane, wu, chunk16, lds_base, aI, m1, m2, tb), misc, w, lane);
+        D_STAMP(2);
+        // (the same in every thread: in a scalar register, so that the loop stays uniform)
+        if (__builtin_amdgcn_readfirstlane(st.bad || !(st.b2max <= T_B2MAX))) {
+            if (t == 0) fallback[pair] = 1;  // outside the keys' range: k_q8d_match redoes the pair
+        } else {
+            const double Bn = sqrt((double)st.b2max) * 1.0001;
+            const double Eb = 8.0001 * (double)st.smax + 1e-30;
+            const unsigned ecnt = epilogue_t(lds, rowv, m1, m2, Bn, Eb, tb, w, lane, n0, n1, A, B, oidx, oscore, thresh,
+                                             reinterpret_cast<const unsigned char *>(lds + T_OFF_COL), rs_flags + pair,
+                                             rs_colsh + (size_t)pair * T_BM);
+            (void)ecnt;
+#ifdef MV_TRACE
+            D_STAMP(3);
+            ts_[8] = ecnt;
+            if (lane == 0 && pair < D_TRACE_BLOCKS) {  // records by pair, not by workgroup
+                unsigned long long *o = g_d_trace + ((size_t)pair * D_NW + w) * 10;
+                for (int k = 0; k < 6; k++) o[k] = ts_[k];  // memtime x 4, memrealtime at entry / after A
+                o[6] = __smid();
+                o[7] = __builtin_amdgcn_s_memrealtime();
+                o[8] = ts_[8];
+                o[9] = ts_[9];
+            }
+#endif
+        }
+        __syncthreads();  // every wave is past its epilogue: the LDS is free for the next pair
+        pair_ = pair_next;
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -1084,7 +1118,8 @@ __global__ __launch_bounds__(64 * RS_NW) void k_q8t_rescan(int batch, int cap, c
                                                            const float *__restrict__ desc1, double thresh,
                                                            int *__restrict__ match_idx, float *__restrict__ match_score,
                                                            const int *__restrict__ rs_flags,
-                                                           const unsigned char *__restrict__ rs_colsh) {
+                                                           const unsigned char *__restrict__ rs_colsh,
+                                                           int *__restrict__ ticket) {
     __shared__ __attribute__((aligned(16))) char bufs[RS_NW][32 * KD];  // per wave: row image / column stage / dots
     __shared__ int cls[RS_NW][64 * RS_CAP];                              // per wave: [row fr][half fh] listed columns
     __shared__ int slotss[RS_NW][32], limss[RS_NW][32];                  // per wave: the batch (identical copies)
@@ -1096,10 +1131,15 @@ __global__ __launch_bounds__(64 * RS_NW) void k_q8t_rescan(int batch, int cap, c
     char *buf = bufs[w];
     int *mycl = cls[w] + (fh * 32 + fr) * RS_CAP;
     int *slots = slotss[w], *lims = limss[w];
-    for (int pair = blockIdx.x; pair < batch; pair += gridDim.x) {
-        const int fl = __builtin_amdgcn_readfirstlane(rs_flags[pair]);
-        if (!fl) continue;  // uniform over the workgroup
-        const int tb = fl - 1;
+    if (blockIdx.x == 0 && t == 0) *ticket = 0;  // k_q8t_match (done: stream order) starts from 0 again
+    // the flag scan: lane l of every wave loads the flag of the workgroup's l-th pair, a ballot gives
+    // 64 answers per round trip -- the same mask in every wave: the walk over its bits is uniform
+    for (long base = blockIdx.x; base < batch; base += 64l * gridDim.x)
+    for (unsigned long long fm = __ballot(base + (long)lane * gridDim.x < batch &&
+                                          rs_flags[min(base + (long)lane * gridDim.x, (long)batch - 1)] != 0);
+         fm; fm &= fm - 1) {
+        const int pair = (int)(base + (long)__builtin_ctzll(fm) * gridDim.x);
+        const int tb = __builtin_amdgcn_readfirstlane(rs_flags[pair]) - 1;
         const int n1 = min(max(n1v[pair], 0), cap);
         const float *A = desc0 + (size_t)pair * cap * KD;
         const float *B = desc1 + (size_t)pair * cap * KD;
@@ -1294,9 +1334,10 @@ int launch_allpairs_q8d_handback(hipStream_t s, int batch, int cap, const int *n
     return MV_OK;
 }
 
-// k_q8t_match (one workgroup per pair) where it applies -- cap <= 1024, the indices / scores
-// match (dmode 0) -- with the pairs it hands back (outside the integer keys' range) redone by
-// k_q8d_match in the same stream: flags[batch] in `scratch` (zeroed here)
+// k_q8t_match (persistent, a whole pair per workgroup and iteration) where it applies -- cap <= 1024,
+// the indices / scores match (dmode 0) -- with the pairs it hands back (outside the integer keys'
+// range) redone by k_q8d_match in the same stream: flags[batch] in `scratch`, zeroed by the kernel
+// itself pair by pair
 bool allpairs_q8t_applies(int cap, int dmode) {
     static const int off = [] {
         const char *e = getenv("MV_Q8_KERNEL");  // "d": k_q8d_match only (A/B of the two layouts)
@@ -1310,25 +1351,33 @@ size_t allpairs_q8t_scratch_bytes(int batch) {
     return 2 * align_up((size_t)batch * 4, 256) + (size_t)batch * T_BM;
 }
 
-int launch_allpairs_q8t_match(hipStream_t s, void *scratch, int batch, int cap, const int *n0, const int *n1,
-                              const float *desc0, const float *desc1, double thresh, int *match_idx,
+int launch_allpairs_q8t_match(hipStream_t s, void *scratch, int *ticket, int cus, int batch, int cap, const int *n0,
+                              const int *n1, const float *desc0, const float *desc1, double thresh, int *match_idx,
                               float *match_score) {
     MV_REQUIRE(batch > 0 && cap > 0 && cap <= T_BM && n0 && n1 && desc0 && desc1 && match_idx && scratch);
+    MV_REQUIRE(ticket && cus > 0);
     MV_REQUIRE(((uintptr_t)desc0 & 15) == 0 && ((uintptr_t)desc1 & 15) == 0);
     const size_t fb = align_up((size_t)batch * 4, 256);
     int *flags = static_cast<int *>(scratch);
     int *rflags = reinterpret_cast<int *>(static_cast<char *>(scratch) + fb);
     unsigned char *rcolsh = static_cast<unsigned char *>(scratch) + 2 * fb;
-    MV_HIP_TRY(hipMemsetAsync(flags, 0, 2 * fb, s));
+    // one workgroup per CU (its LDS fills one); MV_Q8T_GRID (tests): another workgroup count -- with 1,
+    // the pairs run in batch order on one workgroup
+    int grid = min(batch, cus);
+    if (const char *e = getenv("MV_Q8T_GRID")) {
+        const int g = atoi(e);
+        if (g > 0) grid = min(batch, g);
+    }
     MV_PROF_BEGIN(s, "k_q8t_match");
-    hipLaunchKernelGGL(k_q8t_match, dim3((unsigned)batch), dim3(D_NT), 0, s, cap, n0, n1, desc0, desc1, thresh,
-                       match_idx, match_score, flags, rflags, rcolsh);
+    hipLaunchKernelGGL(k_q8t_match, dim3((unsigned)grid), dim3(D_NT), 0, s, batch, cap, n0, n1, desc0, desc1, thresh,
+                       match_idx, match_score, flags, rflags, rcolsh, ticket);
     MV_PROF_END(s);
     MV_LAUNCH_CHECK();
-    // the wide rows it left: 4 waves per workgroup, a grid-stride loop over pairs
+    // the wide rows it left: 4 waves per workgroup, a grid-stride loop over pairs; it also zeroes
+    // the ticket word for the next launch
     MV_PROF_BEGIN(s, "k_q8t_rescan");
     hipLaunchKernelGGL(k_q8t_rescan, dim3((unsigned)min(batch, 1024)), dim3(64 * RS_NW), 0, s, batch, cap, n1, desc0,
-                       desc1, thresh, match_idx, match_score, rflags, rcolsh);
+                       desc1, thresh, match_idx, match_score, rflags, rcolsh, ticket);
     MV_PROF_END(s);
     MV_LAUNCH_CHECK();
     return launch_allpairs_q8d_match(s, batch, cap, n0, n1, desc0, desc1, thresh, match_idx, match_score, 0, flags);

@@ -62,7 +62,7 @@ int ap_match(mv_context *ctx, int screen, hipStream_t s, void *scr, int batch, i
         if (mv::allpairs_q8t_applies(cap, dmode)) {
             void *fl = mv::scratch(ctx, mv::allpairs_q8t_scratch_bytes(batch));
             if (!fl) return MV_ERR_OUT_OF_MEMORY;
-            return mv::launch_allpairs_q8t_match(s, fl, batch, cap, n0, n1, desc0, desc1, thresh, match_idx,
+            return mv::launch_allpairs_q8t_match(s, fl, ctx->q8t_ticket, ctx->cu_count, batch, cap, n0, n1, desc0, desc1, thresh, match_idx,
                                                  match_score);
         }
         return mv::launch_allpairs_q8d_match(s, batch, cap, n0, n1, desc0, desc1, thresh, match_idx, match_score,
@@ -242,8 +242,8 @@ int seq_one_pass_run(mv_context *ctx, int frames, int cap, const int *n, const f
                      int *match_idx, float *match_score) {
     void *fl = mv::scratch(ctx, mv::allpairs_q8t_scratch_bytes(frames - 1));
     if (!fl) return MV_ERR_OUT_OF_MEMORY;
-    return mv::launch_allpairs_q8t_match(ctx->stream, fl, frames - 1, cap, n, n + 1, desc, desc + (size_t)cap * 256,
-                                         thresh, match_idx, match_score);
+    return mv::launch_allpairs_q8t_match(ctx->stream, fl, ctx->q8t_ticket, ctx->cu_count, frames - 1, cap, n, n + 1,
+                                         desc, desc + (size_t)cap * 256, thresh, match_idx, match_score);
 }
 }  // namespace
 

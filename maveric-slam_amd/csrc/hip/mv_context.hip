@@ -177,6 +177,16 @@ int mv_context_create(int device, mv_context **out) {
         return MV_ERR_HIP;
     }
     c->stream = c->own_stream;
+    c->cu_count = prop.multiProcessorCount;
+    if (hipMalloc(reinterpret_cast<void **>(&c->q8t_ticket), 256) != hipSuccess ||
+        hipMemsetAsync(c->q8t_ticket, 0, 256, c->own_stream) != hipSuccess ||
+        hipStreamSynchronize(c->own_stream) != hipSuccess) {
+        if (c->q8t_ticket) (void)hipFree(c->q8t_ticket);
+        (void)hipStreamDestroy(c->own_stream);
+        delete c;
+        mv::set_error(MV_ERR_OUT_OF_MEMORY, "the context's ticket word: allocation failed");
+        return MV_ERR_OUT_OF_MEMORY;
+    }
     const char *scr = getenv("MV_AP_SCREEN");
     c->ap_screen = (scr && strcmp(scr, "f16") == 0)   ? MV_SCREEN_F16
                    : (scr && strcmp(scr, "i8s") == 0) ? MV_SCREEN_I8_STAGED
@@ -200,6 +210,7 @@ int mv_context_destroy(mv_context *ctx) {
     for (const mv_buffer *b : {&ctx->scratch, &ctx->ap_image, &ctx->ap_image2, &ctx->stage})
         if (b->p) (void)hipFree(b->p);
     if (ctx->i8_count_host) (void)hipHostFree(ctx->i8_count_host);
+    if (ctx->q8t_ticket) (void)hipFree(ctx->q8t_ticket);
     (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
     return MV_OK;

@@ -53,6 +53,11 @@ struct mv_context {
     int i8_meas_batch;
     unsigned i8_calls;
     bool i8_prefer_m;  // the last landed measurement: most pairs handed back
+    // k_q8t_match (persistent): the device word its workgroups draw pairs from -- allocated and
+    // zeroed with the context, zeroed again by the kernel that follows each launch; not in `scratch`,
+    // which other entry points write -- and the device's CU count (read once, never under a capture)
+    int *q8t_ticket;
+    int cu_count;
 };
 
 namespace mv {
@@ -154,12 +159,13 @@ int launch_allpairs_q8_match_prepare(hipStream_t s, void *scratch, int batch, in
 int launch_allpairs_q8d_match(hipStream_t s, int batch, int cap, const int *n0, const int *n1, const float *desc0,
                               const float *desc1, double thresh, int *match_idx, float *match_score, int dmode = 0,
                               const int *only = nullptr);
-// the one-workgroup-per-pair transposed kernel (k_allpairs_direct.hip), k_q8d_match for its
-// hand-backs; scratch >= allpairs_q8t_scratch_bytes(batch)
+// the pair-per-workgroup transposed kernel (k_allpairs_direct.hip; persistent, `cus` workgroups
+// drawing pairs from the context's `ticket` word), k_q8d_match for its hand-backs;
+// scratch >= allpairs_q8t_scratch_bytes(batch)
 bool allpairs_q8t_applies(int cap, int dmode);
 size_t allpairs_q8t_scratch_bytes(int batch);
-int launch_allpairs_q8t_match(hipStream_t s, void *scratch, int batch, int cap, const int *n0, const int *n1,
-                              const float *desc0, const float *desc1, double thresh, int *match_idx,
+int launch_allpairs_q8t_match(hipStream_t s, void *scratch, int *ticket, int cus, int batch, int cap, const int *n0,
+                              const int *n1, const float *desc0, const float *desc1, double thresh, int *match_idx,
                               float *match_score);
 size_t allpairs_i8_scratch_bytes(int batch, int cap);
 int launch_allpairs_i8(hipStream_t s, void *scratch, int batch, int cap, const int *n0, const int *n1,

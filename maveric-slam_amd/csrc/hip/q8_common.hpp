@@ -251,6 +251,26 @@ __device__ __forceinline__ void a_phase(char *img, float2 *rowv, int rbase, int 
     }
 }
 
+// max |x| and sum |x|^2 over a row's 16 lanes (quad_perm [1,0,3,2], [2,3,0,1],
+// row_half_mirror, row_mirror), the two reductions interleaved so that every DPP read is two
+// instructions behind the write it reads (no NaN canonicalisation in the max: NaN is caught by
+// |b|^2); every lane of the 16 ends with the same values
+__device__ __forceinline__ void row16_max_sum(float &m, float &q2) {
+    asm("s_nop 1\n\t"
+        "v_max_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+        "v_add_f32_dpp %1, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 0\n\t"
+        "v_max_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+        "v_add_f32_dpp %1, %1, %1 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 0\n\t"
+        "v_max_f32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
+        "v_add_f32_dpp %1, %1, %1 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 0\n\t"
+        "v_max_f32_dpp %0, %0, %0 row_mirror row_mask:0xf bank_mask:0xf\n\t"
+        "v_add_f32_dpp %1, %1, %1 row_mirror row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 1"
+        : "+v"(m), "+v"(q2));
+}
 // a_phase<false, QB, NG> with the loads software-pipelined: batch b + 1's QB row quads are issued
 // before batch b is quantised (two register sets of QB x 4 f32x4), across the group boundaries, so
 // a wave always has 2 QB quads in flight instead of alternating between loading and quantising.
@@ -290,14 +310,9 @@ __device__ __forceinline__ void a_phase_pipe(char *img, float2 *rowv, int rbase,
                 qb = __builtin_fmaf(x[u][3], x[u][3], qb);
             }
             float q2 = qa + qb;
-            m = fmaxf(m, swz_xor<1>(m));
-            q2 += swz_xor<1>(q2);
-            m = fmaxf(m, swz_xor<2>(m));
-            q2 += swz_xor<2>(q2);
-            m = fmaxf(m, swz_xor<4>(m));
-            q2 += swz_xor<4>(q2);
-            m = fmaxf(m, swz_xor<8>(m));
-            q2 += swz_xor<8>(q2);
+            // the 16-lane reductions by DPP (4 VALU steps each, no LDS round trips; the butterfly's
+            // association, so rowv and the codes are what ds_swizzle gave): see row16_max_sum
+            row16_max_sum(m, q2);
             const float q = m > 0.f ? 127.f * __builtin_amdgcn_rcpf(m) : 0.f;
             const bool afull = !(q2 <= FLT_MAX) || m < SCALE_LO || m > SCALE_HI;  // zero rows too
             if (sub == 0) rowv[rbase + g * 32 + r] = make_float2(q2, afull ? -1.f : m * (1.f / 127.f));

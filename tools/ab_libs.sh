@@ -11,6 +11,7 @@ for r in $(seq 1 ${ROUNDS:-2}); do
   for lib in ${LIBS}; do
     n=$(basename $lib .so)
     MV_LIB=$lib timeout -k 10 300 python -u bench.py $ARGS > "$out/${n}_$r.json" 2> "$out/${n}_$r.err"
-    python3 -c "import json; d=json.loads(open('$out/${n}_$r.json').read().strip().splitlines()[-1]); r=d['roofline']; print('$n', 'round $r', d['value'], 'k %.4f ms frac %.4f' % (r['avg_launch_ms'], r['frac']), 'pose', d['stages_ms_per_step'].get('k_pose_ransac'))" | tee -a "$out/summary.log"
+    # (the plain bench line has no roofline / stages: value and ms per step only)
+    python3 -c "import json; d=json.loads(open('$out/${n}_$r.json').read().strip().splitlines()[-1]); r=d.get('roofline'); print('$n', 'round $r', d['value'], 'ms_per_step', d.get('ms_per_step'), ('k %.4f ms frac %.4f' % (r['avg_launch_ms'], r['frac'])) if r else '', 'pose', d.get('stages_ms_per_step', {}).get('k_pose_ransac'))" | tee -a "$out/summary.log"
   done
 done

@@ -1,6 +1,8 @@
 """Phase timing of k_q8t_match (one workgroup per pair; MV_Q8_KERNEL=d: k_q8d_match, two) (library built with EXTRA=-DMV_TRACE, e.g. MV_LIB=
-build_variants/libmaveric_trace.so from tools/build_variant.sh trace -DMV_TRACE): per (block, wave)
-s_memtime stamps at entry, A phase done, sweep + statistics done, epilogue done.
+build_variants/libmaveric_trace.so from tools/build_variant.sh trace -DMV_TRACE): per (pair, wave)
+-- k_q8t_match is persistent: its records are indexed by pair, "blk" below is the pair --
+s_memtime stamps at entry, A phase done, sweep + statistics done, epilogue done; per CU also the
+time from one pair's last stamp to the next pair's first.
 Env: TB pairs (8192), TN per-component noise of the re-observed rows (bench default 0.3/16;
 SURVEY C1: 0.05), TS=1 materialise the exact scores."""
 import ctypes
@@ -53,6 +55,18 @@ o = sel[np.argsort(start[sel])]
 print("distinct CU ids", len(np.unique(sm)), "; CU", cu, "timeline (start, end, dur):")
 for b in o[:12]:
     print("  blk %5d  %9d %9d %9d" % (b, start[b] - start[o[0]], end[b] - start[o[0]], end[b] - start[b]))
+# per CU, from one pair's last stamp (its slowest wave's epilogue end) to the next pair's first
+# stamp (the records are per pair; the persistent kernel runs a CU's pairs in one workgroup):
+# the time a CU spends between pairs; negative once the next pair's prologue overlaps the epilogue
+gaps = []
+for c_ in np.unique(sm):
+    s_ = np.where(sm == c_)[0]
+    s_ = s_[np.argsort(start[s_])]
+    gaps.append(start[s_[1:]] - end[s_[:-1]])
+gaps = np.concatenate(gaps) if gaps else np.zeros(0)
+if gaps.size:
+    print("per CU, last stamp of a pair -> first stamp of the next (cycles): median %.0f, p10 %.0f, p90 %.0f, max %.0f "
+          "(%d gaps)" % (np.median(gaps), np.percentile(gaps, 10), np.percentile(gaps, 90), gaps.max(), gaps.size))
 rt = tr[:, 0, 7]
 a, b = o[0], o[-1]
 if rt[b] != rt[a]:
