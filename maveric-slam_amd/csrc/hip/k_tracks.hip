@@ -1,0 +1,488 @@
+// k_tracks.hip -- feature tracks, triangulated landmarks and BA factors (include/feature_tracks.h).
+// A node is one keypoint slot (s, f, i); a sequence has F * cap nodes, g = f * cap + i.
+//
+// Link (4 launches, every one parallel over all nodes of all sequences, so 2048 x 5 x 512 and
+// 1 x 1025 x 1024 both fill the chip; nothing is swept frame by frame):
+//   k_tr_claim   a workgroup per pair (s, b): cap 64-bit keys in LDS, every proposing row does one
+//                LDS atomicMax with key = (score as an ordered u32) << 32 | ~i -- the key holds
+//                (score, i) completely, so the winner is the same under any schedule.  Writes
+//                acc[s][b][i] = the accepted column or -1 and hasprev[s][b+1][j].
+//   k_tr_roots   a thread per node: a root (no accepted predecessor, an accepted successor) walks
+//                its path through acc and keeps its length when >= min_len; a ballot counts the
+//                kept roots of the 256-node block.  Also writes track_id = -1 everywhere.
+//   k_tr_scan    a workgroup per sequence: exclusive scan of the block counts -> num_tracks,
+//                status, and the unused tails of track_first / track_len.
+//   k_tr_number  a thread per node: track = block offset + ballot prefix (the (frame, row) order
+//                of the first observations); the root writes track_first / track_len and walks its
+//                path again writing track_id.
+// Triangulate: k_tr_triangulate, a thread per track; two walks along match_idx (normal equations,
+//   then depth / reprojection checks), all arithmetic float64 in the order of
+//   tests/tracks_reference.py (no contraction: -ffp-contract=off), the next observation's index,
+//   keypoint, pose and camera loaded before the current one's arithmetic.
+// Factors: k_tr_fcount (ballot count per 256-node block, flat over the batch), k_tr_scan (one
+//   workgroup over the block counts; total, status), k_tr_femit (ballot prefix -> slot; the
+//   first node of every frame writes pose_offsets).
+#include <math.h>
+
+#include "feature_tracks.h"
+#include "mv_internal.hpp"
+
+namespace {
+
+constexpr int NB = 256;  // nodes per workgroup of the per-node kernels
+
+__device__ __forceinline__ int clampn(int v, int cap) { return v < 0 ? 0 : (v > cap ? cap : v); }
+
+// fp32 -> u32 with the order of `<` on non-NaN values (-0 == +0)
+__device__ __forceinline__ unsigned ordered_bits(float f) {
+    if (f == 0.f) f = 0.f;
+    const unsigned u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__global__ __launch_bounds__(256) void k_tr_claim(int F, int cap, const int *__restrict__ n,
+                                                  const int *__restrict__ midx, const float *__restrict__ mscore,
+                                                  int *__restrict__ acc, unsigned char *__restrict__ hasprev) {
+    extern __shared__ unsigned long long s_key[];  // [cap]
+    const int s = blockIdx.x / (F - 1), b = blockIdx.x - s * (F - 1), tid = threadIdx.x;
+    const int n0 = clampn(n[s * F + b], cap), n1 = clampn(n[s * F + b + 1], cap);
+    const size_t pair = ((size_t)s * (F - 1) + b) * cap;
+    const size_t node0 = ((size_t)s * F + b) * cap, node1 = node0 + cap;
+    for (int j = tid; j < cap; j += 256) s_key[j] = 0ull;
+    __syncthreads();
+    for (int i = tid; i < n0; i += 256) {
+        const int j = midx[pair + i];
+        if (j < 0 || j >= n1) continue;
+        unsigned hi = 1u;
+        if (mscore) {
+            const float sc = mscore[pair + i];
+            if (sc != sc) continue;
+            hi = ordered_bits(sc);
+        }
+        atomicMax(&s_key[j], ((unsigned long long)hi << 32) | (unsigned)~i);
+    }
+    __syncthreads();
+    for (int i = tid; i < cap; i += 256) {
+        int a = -1;
+        if (i < n0) {
+            const int j = midx[pair + i];
+            // the low word names the winner (never 0: i >= 0); a row that made no proposal (NaN
+            // score) is never named
+            if (j >= 0 && j < n1 && (unsigned)s_key[j] == (unsigned)~i) a = j;
+        }
+        acc[node0 + i] = a;
+        hasprev[node1 + i] = s_key[i] != 0ull ? 1 : 0;
+        if (b == 0) hasprev[node0 + i] = 0;
+        if (b == F - 2) acc[node1 + i] = -1;
+    }
+}
+
+// length of the path from root (f, i) of sequence s; acc of the last frame is -1
+__device__ __forceinline__ int path_len(const int *__restrict__ acc_s, int F, int cap, int f, int j) {
+    int len = 1;
+    while (j >= 0 && f + 1 < F) {
+        f++;
+        len++;
+        j = acc_s[(size_t)f * cap + j];
+    }
+    return len;
+}
+
+__global__ __launch_bounds__(NB) void k_tr_roots(int F, int cap, int nb, int min_len, const int *__restrict__ n,
+                                                 const int *__restrict__ acc,
+                                                 const unsigned char *__restrict__ hasprev, int *__restrict__ rootlen,
+                                                 int *__restrict__ blocksum, int *__restrict__ track_id) {
+    const int s = blockIdx.x / nb, blk = blockIdx.x - s * nb;
+    const int N = F * cap, g = blk * NB + threadIdx.x;
+    int keep = 0;
+    if (g < N) {
+        const size_t x = (size_t)s * N + g;
+        const int f = g / cap, i = g - f * cap;
+        int len = 0;
+        if (i < clampn(n[s * F + f], cap) && !hasprev[x]) {
+            const int j = acc[x];
+            if (j >= 0) len = path_len(acc + (size_t)s * N, F, cap, f, j);
+        }
+        keep = len >= min_len ? len : 0;
+        rootlen[x] = keep;
+        track_id[x] = -1;
+    }
+    const int cnt = __syncthreads_count(keep != 0);
+    if (threadIdx.x == 0) blocksum[(size_t)s * nb + blk] = cnt;
+}
+
+// Exclusive scan in place of sums[seg][nb], one workgroup per segment.
+//   mode 0 (link):    num_tracks[seg] = total, status[seg], the tails of track_first / track_len
+//   mode 1 (factors): pose_offsets[last] = total, *status
+__global__ __launch_bounds__(256) void k_tr_scan(int nb, int mode, int limit, int *__restrict__ sums,
+                                                 int *__restrict__ total_out, int *__restrict__ status,
+                                                 int *__restrict__ track_first, int *__restrict__ track_len) {
+    __shared__ int s_part[256];
+    const int seg = blockIdx.x, tid = threadIdx.x;
+    int *v = sums + (size_t)seg * nb;
+    const int per = (nb + 255) / 256, lo = min(tid * per, nb), hi = min(lo + per, nb);
+    int sum = 0;
+    for (int k = lo; k < hi; k++) sum += v[k];
+    s_part[tid] = sum;
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {  // inclusive Hillis-Steele scan of the 256 partials
+        const int add = tid >= off ? s_part[tid - off] : 0;
+        __syncthreads();
+        s_part[tid] += add;
+        __syncthreads();
+    }
+    int run = s_part[tid] - sum;
+    const int total = s_part[255];
+    for (int k = lo; k < hi; k++) {
+        const int c = v[k];
+        v[k] = run;
+        run += c;
+    }
+    const bool over = total > limit;
+    if (tid == 0) {
+        total_out[seg] = total;
+        status[seg] = over ? (int)MV_ERR_CAPACITY : (int)MV_OK;
+    }
+    if (mode == 0) {
+        for (int t = (over ? 0 : total) + tid; t < limit; t += 256) {
+            track_first[(size_t)seg * limit + t] = -1;
+            track_len[(size_t)seg * limit + t] = 0;
+        }
+    }
+}
+
+// rank of this thread among the threads of the block with `flag` (NB = 256: 4 waves)
+__device__ __forceinline__ int block_rank(bool flag, int *s_wave) {
+    const unsigned long long m = __ballot(flag);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) s_wave[wave] = __popcll(m);
+    __syncthreads();
+    int r = __popcll(m & ((1ull << lane) - 1ull));
+    for (int w = 0; w < wave; w++) r += s_wave[w];
+    return r;
+}
+
+__global__ __launch_bounds__(NB) void k_tr_number(int F, int cap, int nb, int track_cap, const int *__restrict__ acc,
+                                                  const int *__restrict__ rootlen, const int *__restrict__ blockoff,
+                                                  const int *__restrict__ status, int *__restrict__ track_id,
+                                                  int *__restrict__ track_first, int *__restrict__ track_len) {
+    __shared__ int s_wave[NB / 64];
+    const int s = blockIdx.x / nb, blk = blockIdx.x - s * nb;
+    const int N = F * cap, g = blk * NB + threadIdx.x;
+    const size_t base = (size_t)s * N;
+    const int len = g < N ? rootlen[base + g] : 0;
+    const int t = blockoff[(size_t)s * nb + blk] + block_rank(len != 0, s_wave);
+    if (len == 0 || status[s] != MV_OK || t >= track_cap) return;
+    track_first[(size_t)s * track_cap + t] = g;
+    track_len[(size_t)s * track_cap + t] = len;
+    int f = g / cap, j = g - f * cap;
+    for (int k = 0; k < len && j >= 0 && f < F; k++, f++) {
+        const size_t x = base + (size_t)f * cap + j;
+        track_id[x] = t;
+        j = acc[x];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Triangulation.  Every line below follows tests/tracks_reference.py operation for operation.
+// ---------------------------------------------------------------------------------------------
+struct Obs {
+    double q[7], k[4], u, v;
+};
+
+__device__ __forceinline__ void load_obs(Obs &o, const float *__restrict__ pose, const float *__restrict__ cam,
+                                         const float *__restrict__ kp, size_t frame, size_t node) {
+#pragma unroll
+    for (int c = 0; c < 7; c++) o.q[c] = (double)pose[7 * frame + c];
+#pragma unroll
+    for (int c = 0; c < 4; c++) o.k[c] = (double)cam[4 * frame + c];
+    const float2 p = *reinterpret_cast<const float2 *>(kp + 2 * node);
+    o.u = (double)p.x;
+    o.v = (double)p.y;
+}
+
+__device__ __forceinline__ void rot(const double *q, double *R) {
+    const double w = q[0], x = q[1], y = q[2], z = q[3];
+    const double ww = w * w, xx = x * x, yy = y * y, zz = z * z;
+    R[0] = ((ww + xx) - yy) - zz;
+    R[1] = 2.0 * (x * y - w * z);
+    R[2] = 2.0 * (x * z + w * y);
+    R[3] = 2.0 * (x * y + w * z);
+    R[4] = ((ww - xx) + yy) - zz;
+    R[5] = 2.0 * (y * z - w * x);
+    R[6] = 2.0 * (x * z - w * y);
+    R[7] = 2.0 * (y * z + w * x);
+    R[8] = ((ww - xx) - yy) + zz;
+}
+
+__global__ __launch_bounds__(64) void k_tr_triangulate(int B, int F, int cap, int track_cap, double cos_min,
+                                                       double min_depth, double max_reproj,
+                                                       const float *__restrict__ poses, const float *__restrict__ cams,
+                                                       const float *__restrict__ kp, const int *__restrict__ midx,
+                                                       const int *__restrict__ num_tracks,
+                                                       const int *__restrict__ track_first,
+                                                       const int *__restrict__ track_len, const int *__restrict__ status,
+                                                       float *__restrict__ ldmk, int *__restrict__ flags_out) {
+    const long gt = (long)blockIdx.x * 64 + threadIdx.x;
+    if (gt >= (long)B * track_cap) return;
+    const int s = (int)(gt / track_cap), t = (int)(gt - (long)s * track_cap);
+    const int N = F * cap;
+    int len = 0, first = 0;
+    if (status[s] == MV_OK && t < num_tracks[s]) {
+        first = track_first[gt];
+        len = track_len[gt];
+        if (first < 0 || first >= N) len = 0;
+    }
+    const int f0 = first / cap, i0 = first - f0 * cap;
+    len = min(len, F - f0);
+    if (len <= 0) {  // an unused entry
+        ldmk[3 * gt] = 0.f;
+        ldmk[3 * gt + 1] = 0.f;
+        ldmk[3 * gt + 2] = 0.f;
+        flags_out[gt] = MV_LDMK_DEGENERATE;
+        return;
+    }
+    const size_t fbase = (size_t)s * F, nbase = (size_t)s * N, pbase = (size_t)s * (F - 1) * cap;
+
+    double A00 = 0.0, A01 = 0.0, A02 = 0.0, A11 = 0.0, A12 = 0.0, A22 = 0.0, b0 = 0.0, b1 = 0.0, b2 = 0.0;
+    double c00 = 0.0, c01 = 0.0, c02 = 0.0, e00 = 0.0, e01 = 0.0, e02 = 0.0;
+    double mindot = INFINITY;
+    int count = 0;
+    {
+        Obs cur, nxt;
+        int i = i0, inext = -1;
+        if (len > 0) load_obs(cur, poses, cams, kp, fbase + f0, nbase + (size_t)f0 * cap + i);
+        for (int k = 0; k < len; k++) {
+            const int f = f0 + k;
+            // the next observation's gathers go out before this one's arithmetic
+            inext = -1;
+            if (k + 1 < len) {
+                inext = midx[pbase + (size_t)f * cap + i];
+                if (inext < 0 || inext >= cap) inext = -1;
+            }
+            if (inext >= 0) load_obs(nxt, poses, cams, kp, fbase + f + 1, nbase + (size_t)(f + 1) * cap + inext);
+            double R[9];
+            rot(cur.q, R);
+            const double r0 = (cur.u - cur.k[2]) / cur.k[0], r1 = (cur.v - cur.k[3]) / cur.k[1];
+            const double e0 = (R[0] * r0 + R[3] * r1) + R[6];
+            const double e1 = (R[1] * r0 + R[4] * r1) + R[7];
+            const double e2 = (R[2] * r0 + R[5] * r1) + R[8];
+            const double nrm = sqrt((e0 * e0 + e1 * e1) + e2 * e2);
+            const double d0 = e0 / nrm, d1 = e1 / nrm, d2 = e2 / nrm;
+            const double tx = cur.q[4], ty = cur.q[5], tz = cur.q[6];
+            const double c0 = -((R[0] * tx + R[3] * ty) + R[6] * tz);
+            const double c1 = -((R[1] * tx + R[4] * ty) + R[7] * tz);
+            const double c2 = -((R[2] * tx + R[5] * ty) + R[8] * tz);
+            if (k == 0) {
+                c00 = c0, c01 = c1, c02 = c2;
+                e00 = d0, e01 = d1, e02 = d2;
+            } else {
+                const double dot = (e00 * d0 + e01 * d1) + e02 * d2;
+                if (dot < mindot) mindot = dot;
+            }
+            const double m00 = 1.0 - d0 * d0, m11 = 1.0 - d1 * d1, m22 = 1.0 - d2 * d2;
+            const double m01 = -(d0 * d1), m02 = -(d0 * d2), m12 = -(d1 * d2);
+            A00 = A00 + m00;
+            A01 = A01 + m01;
+            A02 = A02 + m02;
+            A11 = A11 + m11;
+            A12 = A12 + m12;
+            A22 = A22 + m22;
+            const double g0 = c0 - c00, g1 = c1 - c01, g2 = c2 - c02;
+            b0 = b0 + ((m00 * g0 + m01 * g1) + m02 * g2);
+            b1 = b1 + ((m01 * g0 + m11 * g1) + m12 * g2);
+            b2 = b2 + ((m02 * g0 + m12 * g1) + m22 * g2);
+            count++;
+            if (inext < 0) break;
+            cur = nxt;
+            i = inext;
+        }
+    }
+    int flags = 0;
+    if (mindot > cos_min) flags |= MV_LDMK_LOW_PARALLAX;
+    const double C00 = A11 * A22 - A12 * A12, C01 = A02 * A12 - A01 * A22, C02 = A01 * A12 - A02 * A11;
+    const double C11 = A00 * A22 - A02 * A02, C12 = A01 * A02 - A00 * A12, C22 = A00 * A11 - A01 * A01;
+    const double det = (A00 * C00 + A01 * C01) + A02 * C02;
+    const double X0 = c00 + ((C00 * b0 + C01 * b1) + C02 * b2) / det;
+    const double X1 = c01 + ((C01 * b0 + C11 * b1) + C12 * b2) / det;
+    const double X2 = c02 + ((C02 * b0 + C12 * b1) + C22 * b2) / det;
+    const bool finite = isfinite(X0) && isfinite(X1) && isfinite(X2);
+    if (!(det > 0.0) || !finite) {
+        flags |= MV_LDMK_DEGENERATE;
+        ldmk[3 * gt] = 0.f;
+        ldmk[3 * gt + 1] = 0.f;
+        ldmk[3 * gt + 2] = 0.f;
+        flags_out[gt] = flags;
+        return;
+    }
+    const double mr2 = max_reproj * max_reproj;
+    {
+        Obs cur, nxt;
+        int i = i0, inext = -1;
+        load_obs(cur, poses, cams, kp, fbase + f0, nbase + (size_t)f0 * cap + i);
+        for (int k = 0; k < count; k++) {
+            const int f = f0 + k;
+            inext = -1;
+            if (k + 1 < count) inext = midx[pbase + (size_t)f * cap + i];  // in range: walked above
+            if (inext >= 0) load_obs(nxt, poses, cams, kp, fbase + f + 1, nbase + (size_t)(f + 1) * cap + inext);
+            double R[9];
+            rot(cur.q, R);
+            const double p0 = ((R[0] * X0 + R[1] * X1) + R[2] * X2) + cur.q[4];
+            const double p1 = ((R[3] * X0 + R[4] * X1) + R[5] * X2) + cur.q[5];
+            const double p2 = ((R[6] * X0 + R[7] * X1) + R[8] * X2) + cur.q[6];
+            if (p2 < min_depth) flags |= MV_LDMK_BEHIND;
+            const double du = (cur.k[0] * (p0 / p2) + cur.k[2]) - cur.u;
+            const double dv = (cur.k[1] * (p1 / p2) + cur.k[3]) - cur.v;
+            if (du * du + dv * dv > mr2) flags |= MV_LDMK_REPROJ;
+            if (inext < 0) break;
+            cur = nxt;
+            i = inext;
+        }
+    }
+    ldmk[3 * gt] = (float)X0;
+    ldmk[3 * gt + 1] = (float)X1;
+    ldmk[3 * gt + 2] = (float)X2;
+    flags_out[gt] = flags;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Factors
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ int factor_track(long g, long NT, int N, int track_cap, const int *__restrict__ track_id,
+                                            const int *__restrict__ flags) {
+    if (g >= NT) return -1;
+    const int t = track_id[g];
+    if (t < 0 || t >= track_cap) return -1;
+    const long s = g / N;
+    return flags[s * track_cap + t] == 0 ? t : -1;
+}
+
+__global__ __launch_bounds__(NB) void k_tr_fcount(long NT, int N, int track_cap, const int *__restrict__ track_id,
+                                                  const int *__restrict__ flags, int *__restrict__ blocksum) {
+    const long g = (long)blockIdx.x * NB + threadIdx.x;
+    const int cnt = __syncthreads_count(factor_track(g, NT, N, track_cap, track_id, flags) >= 0);
+    if (threadIdx.x == 0) blocksum[blockIdx.x] = cnt;
+}
+
+__global__ __launch_bounds__(NB) void k_tr_femit(long NT, int N, int cap, int track_cap, int factor_cap,
+                                                 const float *__restrict__ kp, const int *__restrict__ track_id,
+                                                 const int *__restrict__ flags, const int *__restrict__ blockoff,
+                                                 int *__restrict__ ldmk_id, int *__restrict__ pose_id,
+                                                 float *__restrict__ meas, int *__restrict__ pose_offsets) {
+    __shared__ int s_wave[NB / 64];
+    const long g = (long)blockIdx.x * NB + threadIdx.x;
+    const int t = factor_track(g, NT, N, track_cap, track_id, flags);
+    const int o = blockoff[blockIdx.x] + block_rank(t >= 0, s_wave);
+    if (g >= NT) return;
+    const long frame = g / cap;  // = s * F + f
+    if (g - frame * cap == 0) pose_offsets[frame] = o;
+    if (t < 0 || o >= factor_cap) return;
+    ldmk_id[o] = (int)(g / N) * track_cap + t;
+    pose_id[o] = (int)frame;
+    *reinterpret_cast<float2 *>(meas + 2l * o) = *reinterpret_cast<const float2 *>(kp + 2 * g);
+}
+
+}  // namespace
+
+extern "C" void mv_landmark_params_default(mv_landmark_params *p) {
+    if (!p) return;
+    p->cos_min_parallax = 0.99984769515639127;  // cos(1 degree)
+    p->min_depth = 0.1;
+    p->max_reproj_px = 2.0;
+}
+
+extern "C" int mv_tracks_link_dev(mv_context *ctx, int batch, int frames, int cap, const int *n, const int *match_idx,
+                                  const float *match_score, int min_len, int track_cap, int *track_id,
+                                  int *num_tracks, int *track_first, int *track_len, int *status) {
+    MV_REQUIRE(ctx && batch > 0 && frames >= 2 && cap >= 1 && cap <= MV_TRACKS_MAX_CAP);
+    MV_REQUIRE(min_len >= 2 && track_cap >= 1);
+    MV_REQUIRE(n && match_idx && track_id && num_tracks && track_first && track_len && status);
+    const long nodes = (long)batch * frames * cap;
+    MV_REQUIRE(nodes < (1l << 31) && (long)batch * track_cap < (1l << 31));
+    MV_HIP_TRY(hipSetDevice(ctx->device));
+    const int N = frames * cap, nb = (N + NB - 1) / NB;
+    const size_t b_acc = mv::align_up((size_t)nodes * 4, 256), b_hp = mv::align_up((size_t)nodes, 256);
+    const size_t b_sum = mv::align_up((size_t)batch * nb * 4, 256);
+    char *d = static_cast<char *>(mv::scratch(ctx, 2 * b_acc + b_hp + b_sum));
+    if (!d) return MV_ERR_OUT_OF_MEMORY;
+    int *acc = reinterpret_cast<int *>(d), *rootlen = reinterpret_cast<int *>(d + b_acc);
+    unsigned char *hasprev = reinterpret_cast<unsigned char *>(d + 2 * b_acc);
+    int *blocksum = reinterpret_cast<int *>(d + 2 * b_acc + b_hp);
+    hipStream_t s = ctx->stream;
+    MV_PROF_BEGIN(s, "k_tr_claim");
+    hipLaunchKernelGGL(k_tr_claim, dim3((unsigned)(batch * (frames - 1))), dim3(256), (size_t)cap * 8, s, frames, cap, n,
+                       match_idx, match_score, acc, hasprev);
+    MV_PROF_END(s);
+    MV_LAUNCH_CHECK();
+    MV_PROF_BEGIN(s, "k_tr_roots");
+    hipLaunchKernelGGL(k_tr_roots, dim3((unsigned)(batch * nb)), dim3(NB), 0, s, frames, cap, nb, min_len, n, acc,
+                       hasprev, rootlen, blocksum, track_id);
+    MV_PROF_END(s);
+    MV_LAUNCH_CHECK();
+    MV_PROF_BEGIN(s, "k_tr_scan");
+    hipLaunchKernelGGL(k_tr_scan, dim3((unsigned)batch), dim3(256), 0, s, nb, 0, track_cap, blocksum, num_tracks, status,
+                       track_first, track_len);
+    MV_PROF_END(s);
+    MV_LAUNCH_CHECK();
+    MV_PROF_BEGIN(s, "k_tr_number");
+    hipLaunchKernelGGL(k_tr_number, dim3((unsigned)(batch * nb)), dim3(NB), 0, s, frames, cap, nb, track_cap, acc,
+                       rootlen, blocksum, status, track_id, track_first, track_len);
+    MV_PROF_END(s);
+    MV_LAUNCH_CHECK();
+    return mv::set_status(MV_OK);
+}
+
+extern "C" int mv_tracks_triangulate_dev(mv_context *ctx, const mv_landmark_params *p, int batch, int frames, int cap,
+                                         int track_cap, const float *poses, const float *cameras, const float *kp,
+                                         const int *match_idx, const int *num_tracks, const int *track_first,
+                                         const int *track_len, const int *status, float *landmarks,
+                                         int *ldmk_flags) {
+    MV_REQUIRE(ctx && p && batch > 0 && frames >= 2 && cap >= 1 && cap <= MV_TRACKS_MAX_CAP && track_cap >= 1);
+    MV_REQUIRE(poses && cameras && kp && match_idx && num_tracks && track_first && track_len && status);
+    MV_REQUIRE(landmarks && ldmk_flags);
+    MV_REQUIRE(((uintptr_t)kp & 7) == 0);  // keypoints are read as float2
+    MV_REQUIRE((long)batch * frames * cap < (1l << 31) && (long)batch * track_cap < (1l << 31));
+    MV_HIP_TRY(hipSetDevice(ctx->device));
+    const long total = (long)batch * track_cap;
+    hipStream_t s = ctx->stream;
+    MV_PROF_BEGIN(s, "k_tr_triangulate");
+    hipLaunchKernelGGL(k_tr_triangulate, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, s, batch, frames, cap,
+                       track_cap, p->cos_min_parallax, p->min_depth, p->max_reproj_px, poses, cameras, kp, match_idx,
+                       num_tracks, track_first, track_len, status, landmarks, ldmk_flags);
+    MV_PROF_END(s);
+    MV_LAUNCH_CHECK();
+    return mv::set_status(MV_OK);
+}
+
+extern "C" int mv_tracks_factors_dev(mv_context *ctx, int batch, int frames, int cap, int track_cap, int factor_cap,
+                                     const float *kp, const int *track_id, const int *ldmk_flags, int *ldmk_id,
+                                     int *pose_id, float *meas, int *pose_offsets, int *status) {
+    MV_REQUIRE(ctx && batch > 0 && frames >= 2 && cap >= 1 && cap <= MV_TRACKS_MAX_CAP && track_cap >= 1);
+    MV_REQUIRE(factor_cap >= 0 && kp && track_id && ldmk_flags && pose_offsets && status);
+    MV_REQUIRE(factor_cap == 0 || (ldmk_id && pose_id && meas));
+    MV_REQUIRE(((uintptr_t)kp & 7) == 0 && ((uintptr_t)meas & 7) == 0);
+    const long NT = (long)batch * frames * cap;
+    MV_REQUIRE(NT < (1l << 31) && (long)batch * track_cap < (1l << 31));
+    MV_HIP_TRY(hipSetDevice(ctx->device));
+    const int nblk = (int)((NT + NB - 1) / NB);
+    int *blocksum = static_cast<int *>(mv::scratch(ctx, (size_t)nblk * 4));
+    if (!blocksum) return MV_ERR_OUT_OF_MEMORY;
+    hipStream_t s = ctx->stream;
+    const int N = frames * cap;
+    MV_PROF_BEGIN(s, "k_tr_fcount");
+    hipLaunchKernelGGL(k_tr_fcount, dim3((unsigned)nblk), dim3(NB), 0, s, NT, N, track_cap, track_id, ldmk_flags,
+                       blocksum);
+    MV_PROF_END(s);
+    MV_LAUNCH_CHECK();
+    MV_PROF_BEGIN(s, "k_tr_scan");
+    hipLaunchKernelGGL(k_tr_scan, dim3(1), dim3(256), 0, s, nblk, 1, factor_cap, blocksum, pose_offsets + batch * frames,
+                       status, (int *)nullptr, (int *)nullptr);
+    MV_PROF_END(s);
+    MV_LAUNCH_CHECK();
+    MV_PROF_BEGIN(s, "k_tr_femit");
+    hipLaunchKernelGGL(k_tr_femit, dim3((unsigned)nblk), dim3(NB), 0, s, NT, N, cap, track_cap, factor_cap, kp, track_id,
+                       ldmk_flags, blocksum, ldmk_id, pose_id, meas, pose_offsets);
+    MV_PROF_END(s);
+    MV_LAUNCH_CHECK();
+    return mv::set_status(MV_OK);
+}

@@ -69,6 +69,15 @@ class TrackParams(ctypes.Structure):
     _fields_ = [("window", WindowParams), ("pose", PoseParams), ("top_n", _I), ("valid_cap", _I)]
 
 
+class LandmarkParams(ctypes.Structure):
+    """mv_landmark_params (include/feature_tracks.h)."""
+    _fields_ = [("cos_min_parallax", _D), ("min_depth", _D), ("max_reproj_px", _D)]
+
+
+LDMK_LOW_PARALLAX, LDMK_BEHIND, LDMK_REPROJ, LDMK_DEGENERATE = 1, 2, 4, 8
+TRACKS_MAX_CAP = 8192  # MV_TRACKS_MAX_CAP
+
+
 def build(force=False):
     """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
     cmd = ["make", "-s", "-C", CSRC, "-j8"]
@@ -184,9 +193,20 @@ def lib():
             "mv_lcd_overlap_dev": (_I, [_P, _I, _I, _P, _I, _P, _P]),
             "mv_lcd_best_dev": (_I, [_P, _I, _I, _P, _I, _P, _P, _P, _P]),
             "mv_lcd_overlap_sorted_host": (_I, [_P, _I, _I, _I, _P, _P, _I, _P, _P]),
+            "mv_landmark_params_default": (None, [_P]),
+            "mv_tracks_link_dev": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
+            "mv_tracks_triangulate_dev": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+            "mv_tracks_factors_dev": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
         }
         for name, (res, args) in sig.items():
-            fn = getattr(L, name)
+            try:
+                fn = getattr(L, name)
+            except AttributeError:
+                # an alternate build (MV_LIB) may predate an entry point: A/B runs that do not use it
+                # still load; using it raises AttributeError.  The shipping build must have them all.
+                if os.environ.get("MV_LIB"):
+                    continue
+                raise
             fn.restype = res
             fn.argtypes = args
         _lib = L
@@ -402,6 +422,48 @@ def track_params(semantics=AS_BUILT):
     p = TrackParams()
     lib().mv_track_params_default(ctypes.byref(p), semantics)
     return p
+
+
+def landmark_params(**kw):
+    """mv_landmark_params (cos_min_parallax cos(1 degree), min_depth 0.1, max_reproj_px 2)."""
+    p = LandmarkParams()
+    lib().mv_landmark_params_default(ctypes.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def poses_to_q7(poses12):
+    """[F][3][4] float64 camera-from-world poses [R | t], as trajectory_chain(..., mode=CHAIN_COMPOSE)
+    gives them, -> [F][7] float32 (qw, qx, qy, qz, tx, ty, tz) with qw >= 0, the pose layout of
+    include/factors.h and Context.tracks_triangulate.  Host, numpy only (not on the hot path).
+    A monocular chain is built from per-pair translations of unit length, so its translations
+    carry no metric scale: the caller supplies the scale (multiply each pair's t before chaining,
+    or the chained t here) -- landmarks triangulated from the poses inherit it."""
+    P = np.asarray(poses12, np.float64).reshape(-1, 3, 4)
+    out = np.zeros((P.shape[0], 7), np.float64)
+    for k in range(P.shape[0]):
+        R = P[k, :, :3]
+        # the largest of the four squared components first (Shepperd): no cancellation
+        d = np.array([1.0 + R[0, 0] + R[1, 1] + R[2, 2], 1.0 + R[0, 0] - R[1, 1] - R[2, 2],
+                      1.0 - R[0, 0] + R[1, 1] - R[2, 2], 1.0 - R[0, 0] - R[1, 1] + R[2, 2]])
+        c = int(np.argmax(d))
+        s = 2.0 * np.sqrt(d[c])
+        if c == 0:
+            q = [0.25 * s, (R[2, 1] - R[1, 2]) / s, (R[0, 2] - R[2, 0]) / s, (R[1, 0] - R[0, 1]) / s]
+        elif c == 1:
+            q = [(R[2, 1] - R[1, 2]) / s, 0.25 * s, (R[0, 1] + R[1, 0]) / s, (R[0, 2] + R[2, 0]) / s]
+        elif c == 2:
+            q = [(R[0, 2] - R[2, 0]) / s, (R[0, 1] + R[1, 0]) / s, 0.25 * s, (R[1, 2] + R[2, 1]) / s]
+        else:
+            q = [(R[1, 0] - R[0, 1]) / s, (R[0, 2] + R[2, 0]) / s, (R[1, 2] + R[2, 1]) / s, 0.25 * s]
+        q = np.array(q)
+        q /= np.sqrt((q * q).sum())
+        if q[0] < 0:
+            q = -q
+        out[k, :4] = q
+        out[k, 4:] = P[k, :, 3]
+    return out.astype(np.float32)
 
 
 def scale_as_built(scale):
@@ -699,6 +761,37 @@ class Context:
         check(lib().mv_pose_from_matches_dev(self.h, ctypes.byref(params), B, cap, _t(n0), _t(match_idx), _t(kp0),
                                              _t(kp1), _t(T), _t(num_matches), _t(num_inliers), _t(status)),
               "pose_from_matches")
+
+    # ---------------- tracks, landmarks, factors (include/feature_tracks.h) ----------------
+    landmark_params = staticmethod(landmark_params)  # also reachable as ctx.landmark_params(**kw)
+
+    def tracks_link(self, n, match_idx, match_score, track_id, num_tracks, track_first, track_len, status, min_len=2):
+        """Device tensors: n [B, F], match_idx / match_score [B, F-1, cap] (match_score may be None)
+        -> track_id [B, F, cap], num_tracks [B], track_first / track_len [B, track_cap], status [B]."""
+        B, F, cap = track_id.shape
+        check(lib().mv_tracks_link_dev(self.h, B, F, cap, _t(n), _t(match_idx), _t(match_score), int(min_len),
+                                       track_first.shape[1], _t(track_id), _t(num_tracks), _t(track_first),
+                                       _t(track_len), _t(status)), "tracks_link")
+
+    def tracks_triangulate(self, poses, cameras, kp, match_idx, num_tracks, track_first, track_len, status, landmarks,
+                           ldmk_flags, params=None):
+        """Device tensors: poses [B, F, 7], cameras [B, F, 4], kp [B, F, cap, 2] and tracks_link's
+        outputs -> landmarks [B, track_cap, 3] float32, ldmk_flags [B, track_cap] int32 (0 = usable)."""
+        B, F, cap = kp.shape[0], kp.shape[1], kp.shape[2]
+        p = params or landmark_params()
+        check(lib().mv_tracks_triangulate_dev(self.h, ctypes.byref(p), B, F, cap, track_first.shape[1], _t(poses),
+                                              _t(cameras), _t(kp), _t(match_idx), _t(num_tracks), _t(track_first),
+                                              _t(track_len), _t(status), _t(landmarks), _t(ldmk_flags)),
+              "tracks_triangulate")
+
+    def tracks_factors(self, kp, track_id, ldmk_flags, ldmk_id, pose_id, meas, pose_offsets, status):
+        """Device tensors: kp [B, F, cap, 2], track_id [B, F, cap], ldmk_flags [B, track_cap] ->
+        ldmk_id / pose_id [factor_cap], meas [factor_cap, 2], pose_offsets [B * F + 1], status [1]:
+        the factor list of projection_factors / pose_normal_equations."""
+        B, F, cap = track_id.shape
+        check(lib().mv_tracks_factors_dev(self.h, B, F, cap, ldmk_flags.shape[1], ldmk_id.shape[0], _t(kp),
+                                          _t(track_id), _t(ldmk_flags), _t(ldmk_id), _t(pose_id), _t(meas),
+                                          _t(pose_offsets), _t(status)), "tracks_factors")
 
     # ---------------- loop closure (include/loop_closure.h) ----------------
     def bow_words(self, voc, desc_scales, desc, num_sel, patches, base, wid, word_id, best_match, scores=None):
