@@ -602,9 +602,9 @@ __global__ __launch_bounds__(D_NT, 2) void k_q8d_handback(int tiles_r, int cap, 
 // the lane half, which the lane itself is) in an SGPR and the shift in a VGPR, one shift per group
 // of 4 consecutive columns (QHalf<true, true>: e uniform over the group, so the 4 shifts of a lane
 // and column block come from one LDS dword).  Per tile and wave: 8 units (jb, g) of 8 MFMAs,
-// every unit folding the previous unit's 16 values (5 VALU per 2 values) beside its MFMAs and
-// reading its fragments from LDS one k32 step ahead; the next tile's quantisation in 7 stages over
-// units 0..3 (half A) and 4..7 (half B).
+// every unit folding the previous unit's 16 values (5 VALU per 2 values) beside its MFMAs; a column
+// block's 8 fragments read from LDS once and kept in registers for its 4 units; the next tile's
+// quantisation in 7 stages over units 0..3 (half A) and 4..7 (half B).
 // Range: a pair whose frame 1 leaves the integer keys' range (a value outside +-1.003, a
 // non-finite value, |b_j|^2 > 4 -- keys then need more than 31 bits at tb = 9) is marked in
 // `fallback` and redone by k_q8d_match (its float path), launched after this kernel with the flags.
@@ -628,7 +628,6 @@ __device__ __forceinline__ int rs_decode(int v) { return (int)((unsigned)v - 0x8
 static_assert(D_OFF_AIMG + D_NW * 32 * KD <= T_OFF_ROW, "A images fit staging slot 2 + the ring");
 static_assert(T_LDS <= 160 * 1024, "one workgroup per CU");
 constexpr float T_B2MAX = 4.f;  // |b_j|^2 bound of the keys' range at tb <= 9
-constexpr int T_PFD = 2;  // k32 steps the frame-1 fragments are read ahead of their MFMA (1: 3.66 ms, 2: 3.53, 3: 3.52 -- profiles/r05g_pfd_ab.json)
 
 __device__ __forceinline__ Sweep sweep_t(char *lds, const float *B, int n1, int t, int lane, int wu, unsigned chunk16,
                                          unsigned lds_base, const i32x4 (&aI)[T_RG][KD / 32], float (&m1)[T_RG],
@@ -680,8 +679,11 @@ __device__ __forceinline__ Sweep sweep_t(char *lds, const float *B, int n1, int 
     // unit U of the tile: column block jb = U >> 2, row group g = U & 3: 8 MFMAs into acc[U & 1],
     // each beside the fold of 2 of the previous unit's 16 values (acc[(U + 1) & 1], row group
     // (U + 3) & 3, shifts PSV, tags PT + r), and quantisation stages 2 (U & 3), 2 (U & 3) + 1 at
-    // k32 steps 0 and 4; the fragments read T_PFD k32 steps ahead across the tile's units (fb_: the
-    // tile's 64 k32 steps, constant indices: only the T_PFD + 1 live ones take registers)
+    // k32 steps 0 and 4.  A column block's 8 fragments (fq_, 32 VGPRs) feed its 4 units and are read
+    // from LDS once: block 0's after the tile's barrier, block 1's during unit 3, each replacing
+    // block 0's fragment of the same k32 step right after that fragment's last MFMA (16 ds_read_b128
+    // per wave and tile where reading per unit took 64).  Measured equal: block 0 streamed two k32
+    // steps ahead by unit 0 and kept (profiles/r10a_fragments_ab.log)
 #define T_UNIT(U, PSV, PT, STG, HH, J0, LIVE)                                                 \
     do {                                                                                     \
         _Pragma("unroll") for (int s_ = 0; s_ < KD / 32; s_++) {                             \
@@ -695,14 +697,13 @@ __device__ __forceinline__ Sweep sweep_t(char *lds, const float *B, int n1, int 
                 else if (k_ == 5) qh.pack23();                                               \
                 else if (k_ == 6) qh.store(rq, (HH), t, (LIVE), st.smax, st.b2max, st.bad, colsh + (tc + 1) * BN); \
             }                                                                                \
-            const int gn_ = 8 * (U) + s_ + T_PFD;                                            \
-            if (gn_ < 64) fb_[gn_] = *reinterpret_cast<const i32x4 *>(rs + rdb + (gn_ >> 5) * 32 * D_RS + 32 * (gn_ & 7)); \
             if (s_ == 0) {                                                                   \
                 const i32x16 z_ = {};                                                        \
-                acc[(U) & 1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fb_[8 * (U)], aI[(U) & 3][0], z_, 0, 0, 0); \
+                acc[(U) & 1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fq_[0], aI[(U) & 3][0], z_, 0, 0, 0); \
             } else {                                                                         \
-                acc[(U) & 1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fb_[8 * (U) + s_], aI[(U) & 3][s_], acc[(U) & 1], 0, 0, 0); \
+                acc[(U) & 1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fq_[s_], aI[(U) & 3][s_], acc[(U) & 1], 0, 0, 0); \
             }                                                                                \
+            if ((U) == 3) fq_[s_] = *reinterpret_cast<const i32x4 *>(rs + rdb + 32 * D_RS + 32 * s_); \
             if (s_ == 0)                                                                     \
                 fold_keys_cv(acc[((U) + 1) & 1][0], acc[((U) + 1) & 1][1], PSV[0], PSV[0], (PT), (PT) + 1u, \
                              m1[((U) + 3) & 3], m2[((U) + 3) & 3]);                          \
@@ -721,9 +722,9 @@ __device__ __forceinline__ Sweep sweep_t(char *lds, const float *B, int n1, int 
             wait_vm<0>();
         }
         D_SYNC();  // tile t complete in its slot; the slot of tile t - 1 and staging of half 2t + 1 free
-        i32x4 fb_[64];
-        _Pragma("unroll") for (int p_ = 0; p_ < T_PFD; p_++)
-            fb_[p_] = *reinterpret_cast<const i32x4 *>(ring + (tc & 1) * D_SLOT + rdb + 32 * p_);
+        i32x4 fq_[KD / 32];  // column block 0 (the ring slot is complete only behind the barrier)
+        _Pragma("unroll") for (int p_ = 0; p_ < KD / 32; p_++)
+            fq_[p_] = *reinterpret_cast<const i32x4 *>(ring + (tc & 1) * D_SLOT + rdb + 32 * p_);
         const int sN = 3 - sA - sB;
         if (2 * tc + 4 < nh) dma_half(B, 2 * tc + 4, n1, wu, chunk16, lds_base + (unsigned)(sN * D_HALF));
         const char *rs = ring + (tc & 1) * D_SLOT;
@@ -1069,9 +1070,22 @@ __global__ __launch_bounds__(D_NT, 2) void k_q8t_match(int batch, int cap, const
         } else {
             const double Bn = sqrt((double)st.b2max) * 1.0001;
             const double Eb = 8.0001 * (double)st.smax + 1e-30;
-            const unsigned ecnt = epilogue_t(lds, rowv, m1, m2, Bn, Eb, tb, w, lane, n0, n1, A, B, oidx, oscore, thresh,
-                                             reinterpret_cast<const unsigned char *>(lds + T_OFF_COL), rs_flags + pair,
-                                             rs_colsh + (size_t)pair * T_BM);
+            // the epilogue's thread index and output pointers rebuilt from the scalar `pair` and the
+            // wave's number behind opaque copies: what the prologue derived from them (the wave's
+            // LDS offset, the output rows' addresses) is not carried across the sweep in vector
+            // registers, which the column block's resident fragments now fill
+            int pe = pair, te;
+            asm volatile("" : "+s"(pe));
+            asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0\n\tv_lshl_add_u32 %0, %1, 6, %0"
+                         : "=&v"(te)
+                         : "s"(wu));
+            __builtin_assume(te >= 0 && te < D_NT);
+            int *oidx_e = match_idx + (size_t)pe * cap;
+            float *oscore_e = match_score ? match_score + (size_t)pe * cap : nullptr;
+            const unsigned ecnt = epilogue_t(lds, rowv, m1, m2, Bn, Eb, tb, te >> 6, te & 63, n0, n1,
+                                             desc0 + (size_t)pe * cap * KD, B, oidx_e, oscore_e, thresh,
+                                             reinterpret_cast<const unsigned char *>(lds + T_OFF_COL), rs_flags + pe,
+                                             rs_colsh + (size_t)pe * T_BM);
             (void)ecnt;
 #ifdef MV_TRACE
             D_STAMP(3);
