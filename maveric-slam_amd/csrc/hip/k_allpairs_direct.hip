@@ -1325,11 +1325,8 @@ int launch_allpairs_q8d_match(hipStream_t s, int batch, int cap, const int *n0, 
     const int tiles_r = (cap + D_BM - 1) / D_BM;
     const long blocks = (long)batch * tiles_r;
     MV_REQUIRE(blocks < (1l << 31));
-    MV_PROF_BEGIN(s, "k_q8d_match");
-    hipLaunchKernelGGL(k_q8d_match, dim3((unsigned)blocks), dim3(D_NT), 0, s, tiles_r, cap, n0, n1, desc0, desc1,
-                       dmode ? -1e300 : thresh, dmode, match_idx, match_score);
-    MV_PROF_END(s);
-    MV_LAUNCH_CHECK();
+    MV_LAUNCH("k_q8d_match", k_q8d_match, dim3((unsigned)blocks), dim3(D_NT), 0, s, tiles_r, cap, n0, n1, desc0, desc1,
+              dmode ? -1e300 : thresh, dmode, match_idx, match_score);
     return MV_OK;
 }
 
@@ -1340,11 +1337,8 @@ int launch_allpairs_q8d_handback(hipStream_t s, int batch, int cap, const int *n
     const int tiles_r = (cap + D_BM - 1) / D_BM;
     const long blocks = (long)batch * tiles_r;
     MV_REQUIRE(blocks < (1l << 31) && (long)cap * KD * 4 < (1l << 32));
-    MV_PROF_BEGIN(s, "k_q8d_handback");
-    hipLaunchKernelGGL(k_q8d_handback, dim3((unsigned)min(blocks, 256l)), dim3(D_NT), 0, s, tiles_r, cap, n0, n1,
-                       desc0, desc1, thresh, match_idx, match_score, only, (int)blocks);
-    MV_PROF_END(s);
-    MV_LAUNCH_CHECK();
+    MV_LAUNCH("k_q8d_handback", k_q8d_handback, dim3((unsigned)min(blocks, 256l)), dim3(D_NT), 0, s, tiles_r, cap, n0,
+              n1, desc0, desc1, thresh, match_idx, match_score, only, (int)blocks);
     return MV_OK;
 }
 
@@ -1359,11 +1353,21 @@ bool allpairs_q8t_applies(int cap, int dmode) {
     }();
     return !off && dmode == 0 && cap > 0 && cap <= T_BM;
 }
-// scratch: [batch] hand-back flags | [batch] re-screen flags (tag width + 1) | [batch][T_BM] the
-// pairs' column key shifts (written only for pairs with re-screened rows)
-size_t allpairs_q8t_scratch_bytes(int batch) {
-    return 2 * align_up((size_t)batch * 4, 256) + (size_t)batch * T_BM;
+struct Q8tScratch {
+    int *flags;             // [batch] hand-back flags
+    int *rflags;            // [batch] re-screen flags (tag width + 1)
+    unsigned char *rcolsh;  // [batch][T_BM] the pairs' column key shifts (written only for pairs with re-screened rows)
+};
+
+static Q8tScratch q8t_scratch_layout(Carve &c, int batch) {
+    Q8tScratch m;
+    m.flags = c.take<int>(batch);
+    m.rflags = c.take<int>(batch);
+    m.rcolsh = c.take<unsigned char>((size_t)batch * T_BM);
+    return m;
 }
+
+size_t allpairs_q8t_scratch_bytes(int batch) { return carve_bytes(q8t_scratch_layout, batch); }
 
 int launch_allpairs_q8t_match(hipStream_t s, void *scratch, int *ticket, int cus, int batch, int cap, const int *n0,
                               const int *n1, const float *desc0, const float *desc1, double thresh, int *match_idx,
@@ -1371,10 +1375,8 @@ int launch_allpairs_q8t_match(hipStream_t s, void *scratch, int *ticket, int cus
     MV_REQUIRE(batch > 0 && cap > 0 && cap <= T_BM && n0 && n1 && desc0 && desc1 && match_idx && scratch);
     MV_REQUIRE(ticket && cus > 0);
     MV_REQUIRE(((uintptr_t)desc0 & 15) == 0 && ((uintptr_t)desc1 & 15) == 0);
-    const size_t fb = align_up((size_t)batch * 4, 256);
-    int *flags = static_cast<int *>(scratch);
-    int *rflags = reinterpret_cast<int *>(static_cast<char *>(scratch) + fb);
-    unsigned char *rcolsh = static_cast<unsigned char *>(scratch) + 2 * fb;
+    Carve scr{static_cast<char *>(scratch)};
+    const Q8tScratch m = q8t_scratch_layout(scr, batch);
     // one workgroup per CU (its LDS fills one); MV_Q8T_GRID (tests): another workgroup count -- with 1,
     // the pairs run in batch order on one workgroup
     int grid = min(batch, cus);
@@ -1382,19 +1384,13 @@ int launch_allpairs_q8t_match(hipStream_t s, void *scratch, int *ticket, int cus
         const int g = atoi(e);
         if (g > 0) grid = min(batch, g);
     }
-    MV_PROF_BEGIN(s, "k_q8t_match");
-    hipLaunchKernelGGL(k_q8t_match, dim3((unsigned)grid), dim3(D_NT), 0, s, batch, cap, n0, n1, desc0, desc1, thresh,
-                       match_idx, match_score, flags, rflags, rcolsh, ticket);
-    MV_PROF_END(s);
-    MV_LAUNCH_CHECK();
+    MV_LAUNCH("k_q8t_match", k_q8t_match, dim3((unsigned)grid), dim3(D_NT), 0, s, batch, cap, n0, n1, desc0, desc1,
+              thresh, match_idx, match_score, m.flags, m.rflags, m.rcolsh, ticket);
     // the wide rows it left: 4 waves per workgroup, a grid-stride loop over pairs; it also zeroes
     // the ticket word for the next launch
-    MV_PROF_BEGIN(s, "k_q8t_rescan");
-    hipLaunchKernelGGL(k_q8t_rescan, dim3((unsigned)min(batch, 1024)), dim3(64 * RS_NW), 0, s, batch, cap, n1, desc0,
-                       desc1, thresh, match_idx, match_score, rflags, rcolsh, ticket);
-    MV_PROF_END(s);
-    MV_LAUNCH_CHECK();
-    return launch_allpairs_q8d_match(s, batch, cap, n0, n1, desc0, desc1, thresh, match_idx, match_score, 0, flags);
+    MV_LAUNCH("k_q8t_rescan", k_q8t_rescan, dim3((unsigned)min(batch, 1024)), dim3(64 * RS_NW), 0, s, batch, cap, n1,
+              desc0, desc1, thresh, match_idx, match_score, m.rflags, m.rcolsh, ticket);
+    return launch_allpairs_q8d_match(s, batch, cap, n0, n1, desc0, desc1, thresh, match_idx, match_score, 0, m.flags);
 }
 
 }  // namespace mv

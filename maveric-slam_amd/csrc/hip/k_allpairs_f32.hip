@@ -557,27 +557,28 @@ __global__ __launch_bounds__(NT, 8 / NW) void k_ap_match(int tiles_r, int cap, c
 
 namespace mv {
 
-// the image: h1 (batch * cap * 512 B) | nrm1 (batch * cap f32) | bad (batch i32)
-size_t allpairs_f32_image_bytes(int batch, int cap) {
-    const size_t rows = (size_t)batch * cap;
-    return rows * ROW_BYTES + align_up(rows * 4, 256) + align_up((size_t)batch * 4, 256);
-}
-
 namespace {
+// the image of k_ap_split
 struct ApScratch {
-    char *h1;
-    float *nrm1;
-    int *bad;
+    char *h1;     // [rows][ROW_BYTES] fp16 rows
+    float *nrm1;  // [rows]
+    int *bad;     // [batch]
 };
-ApScratch ap_scratch_map(void *scratch, int batch, int cap) {
+ApScratch ap_layout(Carve &c, int batch, int cap) {
     const size_t rows = (size_t)batch * cap;
     ApScratch m;
-    m.h1 = (char *)scratch;
-    m.nrm1 = (float *)(m.h1 + rows * ROW_BYTES);
-    m.bad = (int *)((char *)m.nrm1 + align_up(rows * 4, 256));
+    m.h1 = c.take<char>(rows * ROW_BYTES);
+    m.nrm1 = c.take<float>(rows);
+    m.bad = c.take<int>(batch);
     return m;
 }
+ApScratch ap_scratch_map(void *scratch, int batch, int cap) {
+    Carve c{(char *)scratch};
+    return ap_layout(c, batch, cap);
+}
 }  // namespace
+
+size_t allpairs_f32_image_bytes(int batch, int cap) { return carve_bytes(ap_layout, batch, cap); }
 
 // frame 1 -> fp16 image + |b|^2 + per-pair range flag (k_ap_split)
 int launch_allpairs_f32_prepare(hipStream_t s, void *scratch, int batch, int cap, const int *n1,
@@ -589,11 +590,8 @@ int launch_allpairs_f32_prepare(hipStream_t s, void *scratch, int batch, int cap
     const ApScratch m = ap_scratch_map(scratch, batch, cap);
     const long split_blocks = std::min<long>((long)((rows + SPLIT_ROWS - 1) / SPLIT_ROWS), (long)SPLIT_GRID);
     MV_HIP_TRY(hipMemsetAsync(m.bad, 0, (size_t)batch * 4, s));
-    MV_PROF_BEGIN(s, "k_ap_split");
-    hipLaunchKernelGGL(k_ap_split, dim3((unsigned)split_blocks), dim3(256), 0, s, batch, cap, n1, desc1, m.h1, m.nrm1,
-                       m.bad);
-    MV_PROF_END(s);
-    MV_LAUNCH_CHECK();
+    MV_LAUNCH("k_ap_split", k_ap_split, dim3((unsigned)split_blocks), dim3(256), 0, s, batch, cap, n1, desc1, m.h1,
+              m.nrm1, m.bad);
     return MV_OK;
 }
 
@@ -607,11 +605,8 @@ int launch_allpairs_f32_match(hipStream_t s, void *scratch, int batch, int cap, 
     const long blocks = (long)batch * tiles_r;
     MV_REQUIRE(blocks < (1l << 31));
     const ApScratch m = ap_scratch_map(scratch, batch, cap);
-    MV_PROF_BEGIN(s, "k_ap_match");
-    hipLaunchKernelGGL(k_ap_match, dim3((unsigned)blocks), dim3(NT), 0, s, tiles_r, cap, n0, n1, desc0, desc1, m.h1,
-                       m.nrm1, m.bad, dmode ? -1e300 : thresh, dmode, match_idx, match_score);
-    MV_PROF_END(s);
-    MV_LAUNCH_CHECK();
+    MV_LAUNCH("k_ap_match", k_ap_match, dim3((unsigned)blocks), dim3(NT), 0, s, tiles_r, cap, n0, n1, desc0, desc1,
+              m.h1, m.nrm1, m.bad, dmode ? -1e300 : thresh, dmode, match_idx, match_score);
     return MV_OK;
 }
 

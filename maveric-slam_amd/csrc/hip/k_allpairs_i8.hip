@@ -980,11 +980,24 @@ static bool i8_transposed(int cap) {
 static bool i8_keys(int cap) { return i8_transposed(cap) && 2 * ((cap + M_BN - 1) / M_BN) <= 256; }
 static int i8_cap64(int cap) { return (cap + M_BN - 1) / M_BN * M_BN; }
 
-size_t allpairs_i8_scratch_bytes(int batch, int cap) {
+struct I8Scratch {
+    int *nb;     // [batch * cap] frame-1 squared norms
+    float *rnb;  // [batch * cap] their reciprocal square roots
+    int8_t *q1;  // [batch][cap64][KD] the unit-norm code image (i8_keys only)
+    int *flags;  // [batch + 1] k_i8t_match's hand-back flags + their count
+};
+
+static I8Scratch i8_scratch_layout(Carve &c, int batch, int cap) {
     const size_t rows = (size_t)batch * cap;
-    return 2 * align_up(4 * rows, 256) + (i8_keys(cap) ? align_up((size_t)batch * i8_cap64(cap) * KD, 256) : 0) +
-           align_up((size_t)(batch + 1) * 4, 256);  // k_i8t_match's hand-back flags + their count
+    I8Scratch m;
+    m.nb = c.take<int>(rows);
+    m.rnb = c.take<float>(rows);
+    m.q1 = i8_keys(cap) ? c.take<int8_t>((size_t)batch * i8_cap64(cap) * KD) : nullptr;
+    m.flags = c.take<int>((size_t)batch + 1);
+    return m;
 }
+
+size_t allpairs_i8_scratch_bytes(int batch, int cap) { return carve_bytes(i8_scratch_layout, batch, cap); }
 
 int launch_allpairs_i8(hipStream_t s, void *scratch, int batch, int cap, const int *n0, const int *n1,
                        const int8_t *desc0, const int8_t *desc1, int *match_idx, int *match_dot, bool direct,
@@ -992,58 +1005,43 @@ int launch_allpairs_i8(hipStream_t s, void *scratch, int batch, int cap, const i
     MV_REQUIRE(batch > 0 && cap > 0 && n0 && n1 && desc0 && desc1 && match_idx && match_dot && scratch);
     MV_REQUIRE(((uintptr_t)desc0 & 15) == 0 && ((uintptr_t)desc1 & 15) == 0);
     const size_t rows = (size_t)batch * cap;
-    int *nb = (int *)scratch;
-    float *rnb = (float *)((char *)scratch + align_up(4 * rows, 256));
+    Carve scr{(char *)scratch};
+    const I8Scratch m = i8_scratch_layout(scr, batch, cap);
     const bool keys = i8_keys(cap);
     const int cap64 = i8_cap64(cap);
-    int8_t *q1 = keys ? (int8_t *)((char *)scratch + 2 * align_up(4 * rows, 256)) : nullptr;
     const size_t prow = keys ? (size_t)batch * cap64 : rows;
     MV_REQUIRE((prow + 16 * NRM_U - 1) / (16 * NRM_U) < (1l << 31));
     const int nblk = (int)((prow + 16 * NRM_U - 1) / (16 * NRM_U));
-    MV_PROF_BEGIN(s, keys ? "k_i8_prep" : "k_i8_norms");
     if (keys)
-        hipLaunchKernelGGL(k_i8_prep, dim3(nblk), dim3(256), 0, s, batch, cap, cap64, n1, desc1, nb, rnb, q1);
+        MV_LAUNCH("k_i8_prep", k_i8_prep, dim3(nblk), dim3(256), 0, s, batch, cap, cap64, n1, desc1, m.nb, m.rnb, m.q1);
     else
-        hipLaunchKernelGGL(k_i8_norms, dim3(nblk), dim3(256), 0, s, (long)rows, desc1, nb, rnb);
-    MV_PROF_END(s);
-    MV_LAUNCH_CHECK();
+        MV_LAUNCH("k_i8_norms", k_i8_norms, dim3(nblk), dim3(256), 0, s, (long)rows, desc1, m.nb, m.rnb);
     MV_REQUIRE((long)cap * KD < (1l << 31));  // 32-bit DMA source offsets within a pair
     MV_REQUIRE((long)cap64 * KD < (1l << 31));
     if (i8_transposed(cap) && !direct) {
         const int tiles_t = (cap + IT_BM - 1) / IT_BM;
         const long tblocks = (long)batch * tiles_t;
         MV_REQUIRE(tblocks < (1l << 31));
-        int *flags = (int *)((char *)scratch + 2 * align_up(4 * rows, 256) +
-                             align_up((size_t)batch * cap64 * KD, 256));
-        MV_HIP_TRY(hipMemsetAsync(flags, 0, (size_t)(batch + 1) * 4, s));
-        MV_PROF_BEGIN(s, "k_i8t_match");
-        hipLaunchKernelGGL(k_i8t_match, dim3((unsigned)tblocks), dim3(IT_NT), 0, s, tiles_t, cap, n0, n1, desc0, desc1,
-                           nb, match_idx, match_dot, q1, cap64, flags, flags + batch);
-        MV_PROF_END(s);
-        MV_LAUNCH_CHECK();
+        MV_HIP_TRY(hipMemsetAsync(m.flags, 0, (size_t)(batch + 1) * 4, s));
+        MV_LAUNCH("k_i8t_match", k_i8t_match, dim3((unsigned)tblocks), dim3(IT_NT), 0, s, tiles_t, cap, n0, n1, desc0,
+                  desc1, m.nb, match_idx, match_dot, m.q1, cap64, m.flags, m.flags + batch);
         {
             const int tiles_m = (cap + M_BM - 1) / M_BM;
             const long mblocks = (long)batch * tiles_m;
             MV_REQUIRE(mblocks < (1l << 31));
-            MV_PROF_BEGIN(s, "k_i8m_handback");
-            hipLaunchKernelGGL(k_i8m_handback, dim3((unsigned)mblocks), dim3(M_NT), 0, s, tiles_m, cap, n0, n1, desc0,
-                               desc1, nb, rnb, match_idx, match_dot, cap64, flags);
-            MV_PROF_END(s);
-            MV_LAUNCH_CHECK();
-            if (count_host) MV_HIP_TRY(hipMemcpyAsync(count_host, flags + batch, 4, hipMemcpyDeviceToHost, s));
+            MV_LAUNCH("k_i8m_handback", k_i8m_handback, dim3((unsigned)mblocks), dim3(M_NT), 0, s, tiles_m, cap, n0, n1,
+                      desc0, desc1, m.nb, m.rnb, match_idx, match_dot, cap64, m.flags);
+            if (count_host) MV_HIP_TRY(hipMemcpyAsync(count_host, m.flags + batch, 4, hipMemcpyDeviceToHost, s));
         }
         return MV_OK;
     }
     const int tiles_m = (cap + M_BM - 1) / M_BM;
     const long mblocks = (long)batch * tiles_m;
     MV_REQUIRE(mblocks < (1l << 31));
-    MV_PROF_BEGIN(s, "k_i8_match");
     // (with keys: k_i8_prep wrote the unit-norm codes for k_i8t_match; this path reads the norms it
     // also wrote -- the adaptive dispatch's direct calls and cap > 8192)
-    hipLaunchKernelGGL(k_i8_match, dim3((unsigned)mblocks), dim3(M_NT), 0, s, tiles_m, cap, n0, n1, desc0, desc1, nb,
-                       rnb, match_idx, match_dot);
-    MV_PROF_END(s);
-    MV_LAUNCH_CHECK();
+    MV_LAUNCH("k_i8_match", k_i8_match, dim3((unsigned)mblocks), dim3(M_NT), 0, s, tiles_m, cap, n0, n1, desc0, desc1,
+              m.nb, m.rnb, match_idx, match_dot);
     return MV_OK;
 }
 

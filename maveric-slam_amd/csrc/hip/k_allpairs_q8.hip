@@ -402,29 +402,29 @@ __global__ __launch_bounds__(Q_NT, 2) void k_q8_match(int tiles_r, int cap, cons
 
 namespace mv {
 
-// scratch: q1 (rows * 256 B) | s1 | nb2 | eb2 (rows f32 each) | bad (batch i32)
-size_t allpairs_q8_scratch_bytes(int batch, int cap) {
-    const size_t rows = (size_t)batch * cap;
-    return rows * KD + 3 * align_up(rows * 4, 256) + align_up((size_t)batch * 4, 256);
-}
-
 namespace {
 struct Q8Scratch {
-    char *q1;
-    float *s1, *nb2, *eb2;
-    int *bad;
+    char *q1;                // [rows][KD] int8 codes
+    float *s1, *nb2, *eb2;   // [rows] each
+    int *bad;                // [batch]
 };
-Q8Scratch q8_map(void *scratch, int batch, int cap) {
-    const size_t rows = (size_t)batch * cap, fb = align_up(rows * 4, 256);
+Q8Scratch q8_layout(Carve &c, int batch, int cap) {
+    const size_t rows = (size_t)batch * cap;
     Q8Scratch m;
-    m.q1 = (char *)scratch;
-    m.s1 = (float *)(m.q1 + rows * KD);
-    m.nb2 = (float *)((char *)m.s1 + fb);
-    m.eb2 = (float *)((char *)m.nb2 + fb);
-    m.bad = (int *)((char *)m.eb2 + fb);
+    m.q1 = c.take<char>(rows * KD);
+    m.s1 = c.take<float>(rows);
+    m.nb2 = c.take<float>(rows);
+    m.eb2 = c.take<float>(rows);
+    m.bad = c.take<int>(batch);
     return m;
 }
+Q8Scratch q8_map(void *scratch, int batch, int cap) {
+    Carve c{(char *)scratch};
+    return q8_layout(c, batch, cap);
+}
 }  // namespace
+
+size_t allpairs_q8_scratch_bytes(int batch, int cap) { return carve_bytes(q8_layout, batch, cap); }
 
 int launch_allpairs_q8_prepare(hipStream_t s, void *scratch, int batch, int cap, const int *n1, const float *desc1) {
     MV_REQUIRE(batch > 0 && cap > 0 && n1 && desc1 && scratch);
@@ -434,11 +434,8 @@ int launch_allpairs_q8_prepare(hipStream_t s, void *scratch, int batch, int cap,
     const Q8Scratch m = q8_map(scratch, batch, cap);
     const long blocks = std::min<long>((long)((rows + QS_ROWS - 1) / QS_ROWS), (long)QS_GRID);
     MV_HIP_TRY(hipMemsetAsync(m.bad, 0, (size_t)batch * 4, s));
-    MV_PROF_BEGIN(s, "k_q8_split");
-    hipLaunchKernelGGL(k_q8_split, dim3((unsigned)blocks), dim3(256), 0, s, batch, cap, n1, desc1, m.q1, m.s1, m.nb2,
-                       m.eb2, m.bad);
-    MV_PROF_END(s);
-    MV_LAUNCH_CHECK();
+    MV_LAUNCH("k_q8_split", k_q8_split, dim3((unsigned)blocks), dim3(256), 0, s, batch, cap, n1, desc1, m.q1, m.s1,
+              m.nb2, m.eb2, m.bad);
     return MV_OK;
 }
 
@@ -463,13 +460,10 @@ int launch_allpairs_q8_match_prepare(hipStream_t s, void *scratch, int batch, in
         nrows = (long)next_batch * next_cap;
         MV_HIP_TRY(hipMemsetAsync(nm.bad, 0, (size_t)next_batch * 4, s));
     }
-    MV_PROF_BEGIN(s, "k_q8_match");
-    hipLaunchKernelGGL(k_q8_match<false>, dim3((unsigned)blocks), dim3(Q_NT), 0, s, tiles_r, cap, n0, n1, desc0,
-                       desc1, m.q1, m.s1, m.nb2, m.eb2, m.bad, dmode ? -1e300 : thresh, dmode, match_idx, match_score,
-                       nrows, next_cap, next_n1, next_desc1, nm.q1, nm.s1, nm.nb2, nm.eb2, nm.bad,
-                       (const char *)nullptr, (const float *)nullptr, (const float *)nullptr, (const int *)nullptr);
-    MV_PROF_END(s);
-    MV_LAUNCH_CHECK();
+    MV_LAUNCH("k_q8_match", k_q8_match<false>, dim3((unsigned)blocks), dim3(Q_NT), 0, s, tiles_r, cap, n0, n1, desc0,
+              desc1, m.q1, m.s1, m.nb2, m.eb2, m.bad, dmode ? -1e300 : thresh, dmode, match_idx, match_score, nrows,
+              next_cap, next_n1, next_desc1, nm.q1, nm.s1, nm.nb2, nm.eb2, nm.bad, (const char *)nullptr,
+              (const float *)nullptr, (const float *)nullptr, (const int *)nullptr);
     return MV_OK;
 }
 
@@ -512,13 +506,10 @@ int launch_allpairs_q8_sequence(hipStream_t s, void *scratch, int frames, int ca
         MV_HIP_TRY(hipMemsetAsync(nm.bad, 0, (size_t)next_frames * 4, s));
     }
     const size_t fr = (size_t)cap;
-    MV_PROF_BEGIN(s, "k_q8_match_seq");
-    hipLaunchKernelGGL(k_q8_match<true>, dim3((unsigned)blocks), dim3(Q_NT), 0, s, tiles_r, cap, n, n + 1, desc,
-                       desc + fr * KD, m.q1 + fr * KD, m.s1 + fr, m.nb2 + fr, m.eb2 + fr, m.bad + 1, thresh, 0,
-                       match_idx, match_score, nrows, next_cap, next_n, next_desc, nm.q1, nm.s1, nm.nb2, nm.eb2,
-                       nm.bad, (const char *)m.q1, (const float *)m.s1, (const float *)m.nb2, (const int *)m.bad);
-    MV_PROF_END(s);
-    MV_LAUNCH_CHECK();
+    MV_LAUNCH("k_q8_match_seq", k_q8_match<true>, dim3((unsigned)blocks), dim3(Q_NT), 0, s, tiles_r, cap, n, n + 1,
+              desc, desc + fr * KD, m.q1 + fr * KD, m.s1 + fr, m.nb2 + fr, m.eb2 + fr, m.bad + 1, thresh, 0, match_idx,
+              match_score, nrows, next_cap, next_n, next_desc, nm.q1, nm.s1, nm.nb2, nm.eb2, nm.bad, (const char *)m.q1,
+              (const float *)m.s1, (const float *)m.nb2, (const int *)m.bad);
     return MV_OK;
 }
 

@@ -272,14 +272,27 @@ __global__ __launch_bounds__(256) void k_lcd_best(int F, const int *__restrict__
     }
 }
 
+// the vocabulary image, on the host and on the device
+struct VocImage {
+    float *scale, *bias;  // [nb] each
+    int8_t *base_desc;    // [nb][256]
+    uint4 *leaf;          // [nb][wpb]
+};
+
+VocImage voc_layout(mv::Carve &c, size_t nb, size_t wpb) {
+    VocImage m;
+    m.scale = c.take<float>(nb);
+    m.bias = c.take<float>(nb);
+    m.base_desc = c.take<int8_t>(256 * nb);
+    m.leaf = c.take<uint4>(nb * wpb);
+    return m;
+}
+
 bool aligned_to(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 int launch_overlap(hipStream_t s, int S, int Q, const uint32_t *q_bits, int F, const uint32_t *db_bits, int *counts) {
-    MV_PROF_BEGIN(s, "k_lcd_overlap");
-    hipLaunchKernelGGL(k_lcd_overlap, dim3((unsigned)((F + OT - 1) / OT), (unsigned)((Q + OT - 1) / OT)), dim3(256), 0,
-                       s, Q, F, S, q_bits, db_bits, counts);
-    MV_PROF_END(s);
-    MV_LAUNCH_CHECK();
+    MV_LAUNCH("k_lcd_overlap", k_lcd_overlap, dim3((unsigned)((F + OT - 1) / OT), (unsigned)((Q + OT - 1) / OT)),
+              dim3(256), 0, s, Q, F, S, q_bits, db_bits, counts);
     return MV_OK;
 }
 
@@ -295,37 +308,38 @@ extern "C" int mv_vocabulary_create(mv_context *ctx, int num_base, int words_per
     MV_REQUIRE((long)num_base * words_per_base < (1l << 31));
     MV_HIP_TRY(hipSetDevice(ctx->device));
     const size_t nb = (size_t)num_base, wpb = (size_t)words_per_base;
-    const size_t o_bias = mv::align_up(nb * 4, 256), o_bd = o_bias + mv::align_up(nb * 4, 256);
-    const size_t o_leaf = o_bd + mv::align_up(256 * nb, 256), bytes = o_leaf + nb * wpb * 16;
-    char *h = static_cast<char *>(calloc(bytes, 1));
-    if (!h) return mv::set_status(MV_ERR_OUT_OF_MEMORY);
-    memcpy(h, scale, nb * 4);
-    memcpy(h + o_bias, bias, nb * 4);
-    memcpy(h + o_bd, base_desc, 256 * nb);
-    memcpy(h + o_leaf, leaf, nb * wpb * 16);
+    const size_t bytes = mv::carve_bytes(voc_layout, nb, wpb);
+    mv::Carve h{static_cast<char *>(calloc(bytes, 1))};
+    if (!h.base) return mv::set_status(MV_ERR_OUT_OF_MEMORY);
+    const VocImage hi = voc_layout(h, nb, wpb);
+    memcpy(hi.scale, scale, nb * 4);
+    memcpy(hi.bias, bias, nb * 4);
+    memcpy(hi.base_desc, base_desc, 256 * nb);
+    memcpy(hi.leaf, leaf, nb * wpb * 16);
     mv_vocabulary *v = new mv_vocabulary();
     v->device = ctx->device;
     v->nb = num_base;
     v->wpb = words_per_base;
     if (hipMalloc(&v->dev, bytes) != hipSuccess) {
-        free(h);
+        free(h.base);
         delete v;
         mv::set_error(MV_ERR_OUT_OF_MEMORY, "vocabulary allocation of %zu bytes failed", bytes);
         return MV_ERR_OUT_OF_MEMORY;
     }
-    const hipError_t e = hipMemcpy(v->dev, h, bytes, hipMemcpyHostToDevice);
-    free(h);
+    const hipError_t e = hipMemcpy(v->dev, h.base, bytes, hipMemcpyHostToDevice);
+    free(h.base);
     if (e != hipSuccess) {
         (void)hipFree(v->dev);
         delete v;
         mv::set_error(MV_ERR_HIP, "hipMemcpy of the vocabulary: %s", hipGetErrorString(e));
         return MV_ERR_HIP;
     }
-    const char *d = static_cast<const char *>(v->dev);
-    v->scale = reinterpret_cast<const float *>(d);
-    v->bias = reinterpret_cast<const float *>(d + o_bias);
-    v->base_desc = reinterpret_cast<const int8_t *>(d + o_bd);
-    v->leaf = reinterpret_cast<const uint4 *>(d + o_leaf);
+    mv::Carve d{static_cast<char *>(v->dev)};
+    const VocImage di = voc_layout(d, nb, wpb);
+    v->scale = di.scale;
+    v->bias = di.bias;
+    v->base_desc = di.base_desc;
+    v->leaf = di.leaf;
     *out = v;
     return mv::set_status(MV_OK);
 }
@@ -353,12 +367,9 @@ extern "C" int mv_bow_words_batch_dev(mv_context *ctx, const mv_vocabulary *voc,
     const size_t dyn = (size_t)FPB * voc->nb * 4 + (size_t)256 * voc->nb;
     const dim3 grid((unsigned)((total + FPB - 1) / FPB));
     hipStream_t s = ctx->stream;
-    MV_PROF_BEGIN(s, "k_bow_words");
-    hipLaunchKernelGGL(k_bow_words, grid, dim3(256), dyn, s, total, N, cells, voc->nb, voc->wpb, desc_scales, desc,
-                       num_sel, patches, voc->scale, voc->bias, voc->base_desc, voc->leaf, base, wid, word_id,
-                       best_match, scores);
-    MV_PROF_END(s);
-    MV_LAUNCH_CHECK();
+    MV_LAUNCH("k_bow_words", k_bow_words, grid, dim3(256), dyn, s, total, N, cells, voc->nb, voc->wpb, desc_scales,
+              desc, num_sel, patches, voc->scale, voc->bias, voc->base_desc, voc->leaf, base, wid, word_id, best_match,
+              scores);
     return mv::set_status(MV_OK);
 }
 
@@ -369,22 +380,24 @@ extern "C" int mv_bow_words_host(mv_context *ctx, const mv_vocabulary *voc, int 
     if (num_sel == 0) return mv::set_status(MV_OK);
     MV_REQUIRE(patches && base && wid && word_id && best_match);
     MV_HIP_TRY(hipSetDevice(ctx->device));
-    const size_t n = (size_t)num_sel, bdesc = mv::align_up((size_t)cells * 256, 256), bn = mv::align_up(n * 4, 256);
-    const size_t bsc = mv::align_up(n * voc->nb * 4, 256);
-    char *d = static_cast<char *>(mv::stage(ctx, 512 + bdesc + 5 * bn + bsc));
-    if (!d) return MV_ERR_OUT_OF_MEMORY;
-    float *d_scale = reinterpret_cast<float *>(d);
-    int *d_ns = reinterpret_cast<int *>(d + 256);
-    int8_t *d_desc = reinterpret_cast<int8_t *>(d + 512);
-    int *d_pa = reinterpret_cast<int *>(d + 512 + bdesc);
-    int *d_out = reinterpret_cast<int *>(d + 512 + bdesc + bn);  // base | wid | word_id | best_match
-    float *d_sc = reinterpret_cast<float *>(d + 512 + bdesc + 5 * bn);
+    const size_t n = (size_t)num_sel;
+    float *d_scale, *d_sc;
+    int *d_ns, *d_pa, *o[4];  // o: base | wid | word_id | best_match
+    int8_t *d_desc;
+    if (!mv::carve(mv::stage, ctx, [&](mv::Carve &c) {
+            d_scale = c.take<float>(1);
+            d_ns = c.take<int>(1);
+            d_desc = c.take<int8_t>((size_t)cells * 256);
+            d_pa = c.take<int>(n);
+            for (int x = 0; x < 4; x++) o[x] = c.take<int>(n);
+            d_sc = c.take<float>(n * voc->nb);
+        }))
+        return MV_ERR_OUT_OF_MEMORY;
     hipStream_t s = ctx->stream;
     MV_HIP_TRY(hipMemcpyAsync(d_scale, &desc_scale, 4, hipMemcpyHostToDevice, s));
     MV_HIP_TRY(hipMemcpyAsync(d_ns, &num_sel, 4, hipMemcpyHostToDevice, s));
     MV_HIP_TRY(hipMemcpyAsync(d_desc, desc, (size_t)cells * 256, hipMemcpyHostToDevice, s));
     MV_HIP_TRY(hipMemcpyAsync(d_pa, patches, n * 4, hipMemcpyHostToDevice, s));
-    int *o[4] = {d_out, d_out + bn / 4, d_out + 2 * (bn / 4), d_out + 3 * (bn / 4)};
     const int st = mv_bow_words_batch_dev(ctx, voc, 1, cells, num_sel, d_scale, d_desc, d_ns, d_pa, o[0], o[1], o[2],
                                           o[3], scores ? d_sc : nullptr);
     if (st != MV_OK) return st;
@@ -411,11 +424,8 @@ extern "C" int mv_word_sets_batch_dev(mv_context *ctx, int num_words, int batch,
     MV_HIP_TRY(hipMemsetAsync(bits, 0, (size_t)batch * S * 4, s));
     MV_HIP_TRY(hipMemsetAsync(distinct, 0, (size_t)batch * 4, s));
     if (total > 0) {
-        MV_PROF_BEGIN(s, "k_word_sets");
-        hipLaunchKernelGGL(k_word_sets, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, total, N, num_words, S,
-                           word_id, bits, distinct);
-        MV_PROF_END(s);
-        MV_LAUNCH_CHECK();
+        MV_LAUNCH("k_word_sets", k_word_sets, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, total, N,
+                  num_words, S, word_id, bits, distinct);
     }
     return mv::set_status(MV_OK);
 }
@@ -441,10 +451,7 @@ extern "C" int mv_lcd_best_dev(mv_context *ctx, int num_words, int Q, const uint
     hipStream_t s = ctx->stream;
     const int st = launch_overlap(s, mv_word_set_stride(num_words), Q, q_bits, F, db_bits, counts);
     if (st != MV_OK) return st;
-    MV_PROF_BEGIN(s, "k_lcd_best");
-    hipLaunchKernelGGL(k_lcd_best, dim3((unsigned)Q), dim3(256), 0, s, F, counts, limit, best_frame, best_count);
-    MV_PROF_END(s);
-    MV_LAUNCH_CHECK();
+    MV_LAUNCH("k_lcd_best", k_lcd_best, dim3((unsigned)Q), dim3(256), 0, s, F, counts, limit, best_frame, best_count);
     return mv::set_status(MV_OK);
 }
 
@@ -468,8 +475,15 @@ extern "C" int mv_lcd_overlap_sorted_host(mv_context *ctx, int num_words, int F,
     }
     MV_HIP_TRY(hipSetDevice(ctx->device));
     const size_t rows = (size_t)F + 1, S = (size_t)mv_word_set_stride(num_words);
-    const size_t bids = mv::align_up(rows * cap * 4, 256), bbits = mv::align_up(rows * S * 4, 256);
-    const size_t brow = mv::align_up(rows * 4, 256);
+    int *d_ids, *d_distinct, *d_counts;
+    uint32_t *d_bits;
+    if (!mv::carve(mv::stage, ctx, [&](mv::Carve &c) {
+            d_ids = c.take<int>(rows * cap);
+            d_bits = c.take<uint32_t>(rows * S);
+            d_distinct = c.take<int>(rows);
+            d_counts = c.take<int>(rows);
+        }))
+        return MV_ERR_OUT_OF_MEMORY;
     int *h = static_cast<int *>(malloc(rows * cap * 4));
     if (!h) return mv::set_status(MV_ERR_OUT_OF_MEMORY);
     for (size_t f = 0; f < rows; f++) {
@@ -477,15 +491,6 @@ extern "C" int mv_lcd_overlap_sorted_host(mv_context *ctx, int num_words, int F,
         const int *ids = f < (size_t)F ? prev_ids + f * cap : cur_ids;
         for (int i = 0; i < cap; i++) h[f * cap + i] = i < n ? ids[i] : -1;
     }
-    char *d = static_cast<char *>(mv::stage(ctx, bids + bbits + 2 * brow));
-    if (!d) {
-        free(h);
-        return MV_ERR_OUT_OF_MEMORY;
-    }
-    int *d_ids = reinterpret_cast<int *>(d);
-    uint32_t *d_bits = reinterpret_cast<uint32_t *>(d + bids);
-    int *d_distinct = reinterpret_cast<int *>(d + bids + bbits);
-    int *d_counts = reinterpret_cast<int *>(d + bids + bbits + brow);
     hipStream_t s = ctx->stream;
     hipError_t e = hipMemcpyAsync(d_ids, h, rows * cap * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);  // h is pageable: done with it before the free

@@ -117,10 +117,7 @@ extern "C" int mv_run_nms_batch_dev(mv_context *ctx, int batch, int rows, int co
     MV_REQUIRE(ctx && batch > 0 && rows > 0 && cols > 0 && max_idx && probs && num_kp && kp);
     MV_REQUIRE((long)rows * cols <= CNMS_MAX_CELLS);
     MV_HIP_TRY(hipSetDevice(ctx->device));
-    MV_PROF_BEGIN(ctx->stream, "k_run_nms");
-    hipLaunchKernelGGL(k_run_nms, dim3((unsigned)batch), dim3(64), 0, ctx->stream, rows, cols, max_idx, probs, num_kp,
-                       kp);
-    MV_PROF_END(ctx->stream);
-    MV_LAUNCH_CHECK();
+    MV_LAUNCH("k_run_nms", k_run_nms, dim3((unsigned)batch), dim3(64), 0, ctx->stream, rows, cols, max_idx, probs,
+              num_kp, kp);
     return mv::set_status(MV_OK);
 }

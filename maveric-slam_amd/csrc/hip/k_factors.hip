@@ -142,11 +142,8 @@ extern "C" int mv_projection_factors_dev(mv_context *ctx, int num_factors, const
     MV_REQUIRE(!J || ((uintptr_t)J & 15) == 0);
     if (num_factors == 0) return mv::set_status(MV_OK);
     MV_HIP_TRY(hipSetDevice(ctx->device));
-    MV_PROF_BEGIN(ctx->stream, "k_pf_linearize");
-    hipLaunchKernelGGL(k_pf_linearize, dim3((unsigned)((num_factors + 255) / 256)), dim3(256), 0, ctx->stream,
-                       num_factors, landmarks, poses, cameras, ldmk_id, pose_id, meas, err, J, H);
-    MV_PROF_END(ctx->stream);
-    MV_LAUNCH_CHECK();
+    MV_LAUNCH("k_pf_linearize", k_pf_linearize, dim3((unsigned)((num_factors + 255) / 256)), dim3(256), 0, ctx->stream,
+              num_factors, landmarks, poses, cameras, ldmk_id, pose_id, meas, err, J, H);
     return mv::set_status(MV_OK);
 }
 
@@ -154,9 +151,6 @@ extern "C" int mv_pose_normal_equations_dev(mv_context *ctx, int num_poses, cons
                                             float *HPP, float *g, float *ee) {
     MV_REQUIRE(ctx && num_poses > 0 && pose_offsets && J && HPP && g && ee);
     MV_HIP_TRY(hipSetDevice(ctx->device));
-    MV_PROF_BEGIN(ctx->stream, "k_pose_ne");
-    hipLaunchKernelGGL(k_pose_ne, dim3((unsigned)num_poses), dim3(64), 0, ctx->stream, pose_offsets, J, HPP, g, ee);
-    MV_PROF_END(ctx->stream);
-    MV_LAUNCH_CHECK();
+    MV_LAUNCH("k_pose_ne", k_pose_ne, dim3((unsigned)num_poses), dim3(64), 0, ctx->stream, pose_offsets, J, HPP, g, ee);
     return mv::set_status(MV_OK);
 }

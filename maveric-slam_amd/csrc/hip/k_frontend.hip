@@ -1244,22 +1244,16 @@ int launch_softmax(hipStream_t s, int batch, int cells, const float *scales, con
     const long rows = (long)batch * cells;
     MV_HIP_TRY(hipMemsetAsync(num_valid, 0, sizeof(int) * batch, s));
     const int blocks = (int)((rows + 255) / 256);
-    MV_PROF_BEGIN(s, "k_softmax");
-    hipLaunchKernelGGL(k_softmax, dim3(blocks), dim3(256), 0, s, (int)rows, cells, scales, semi, max_idx, probs,
-                       num_valid);
-    MV_PROF_END(s);
-    MV_LAUNCH_CHECK();
+    MV_LAUNCH("k_softmax", k_softmax, dim3(blocks), dim3(256), 0, s, (int)rows, cells, scales, semi, max_idx, probs,
+              num_valid);
     return MV_OK;
 }
 
 int launch_top_n_select(hipStream_t s, int batch, int cells, const int *max_idx, const float *probs, int N,
                         int cap, int *num_sel, int *patches, int *indices, float *sel_probs, int *status) {
     MV_REQUIRE(batch > 0 && cells > 0 && N > 0 && cap > 0);
-    MV_PROF_BEGIN(s, "k_top_n_select");
-    hipLaunchKernelGGL(k_top_n_select, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, s, batch, cells, max_idx,
-                       probs, N, cap, num_sel, patches, indices, sel_probs, status);
-    MV_PROF_END(s);
-    MV_LAUNCH_CHECK();
+    MV_LAUNCH("k_top_n_select", k_top_n_select, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, s, batch, cells,
+              max_idx, probs, N, cap, num_sel, patches, indices, sel_probs, status);
     return MV_OK;
 }
 
@@ -1290,18 +1284,17 @@ extern "C" int mv_window_match_batch_dev(mv_context *ctx, const mv_window_params
     // fast path: one mask word per column and a window list that fits the wave's LDS slice
     const int wside = 2 * p->radius + 1;
     const bool fast = rows <= 64 && p->radius >= 0 && wside <= 64 && (long)wside * min(wside, rows) <= kWinList;
-    const size_t qr_bytes = mv::align_up(sizeof(QueryResult) * (size_t)batch * N, 256);
-    char *sc = (char *)mv::scratch(ctx, qr_bytes + (fast ? sizeof(unsigned long long) * (size_t)batch * cols : 0));
-    if (!sc) return MV_ERR_OUT_OF_MEMORY;
-    QueryResult *qr = (QueryResult *)sc;
+    QueryResult *qr;
+    unsigned long long *masks = nullptr;  // fast only
+    if (!mv::carve(mv::scratch, ctx, [&](mv::Carve &c) {
+            qr = c.take<QueryResult>((size_t)batch * N);
+            if (fast) masks = c.take<unsigned long long>((size_t)batch * cols);
+        }))
+        return MV_ERR_OUT_OF_MEMORY;
     if (fast) {
-        unsigned long long *masks = (unsigned long long *)(sc + qr_bytes);
         const long tcols = (long)batch * cols;
-        MV_PROF_BEGIN(ctx->stream, "k_window_mask");
-        hipLaunchKernelGGL(k_window_mask, dim3((unsigned)((tcols + 255) / 256)), dim3(256), 0, ctx->stream, tcols, rows,
-                           max_idx0, probs0, a.prob_thr, masks);
-        MV_PROF_END(ctx->stream);
-        MV_LAUNCH_CHECK();
+        MV_LAUNCH("k_window_mask", k_window_mask, dim3((unsigned)((tcols + 255) / 256)), dim3(256), 0, ctx->stream,
+                  tcols, rows, max_idx0, probs0, a.prob_thr, masks);
         const bool tiled = !a.as_built && kBandW + 2 * p->radius <= 64 && cells <= 65536 && cols <= 1024 &&
                            (long)(kBandW + 2 * p->radius) * rows <= kBandList;
         if (tiled) {
@@ -1309,38 +1302,25 @@ extern "C" int mv_window_match_batch_dev(mv_context *ctx, const mv_window_params
             const long nblk = (long)bpp * batch;
             MV_REQUIRE(nblk < (1l << 30));
             const unsigned g = (unsigned)((nblk + 7) / 8 * 8);
-            MV_PROF_BEGIN(ctx->stream, "k_window_eval");
-            hipLaunchKernelGGL(k_window_wave, dim3(g), dim3(256), 0, ctx->stream, a, bpp, (int)nblk, masks, desc0,
-                               desc1, num_selected, patches1, qr);
-            MV_PROF_END(ctx->stream);
-            MV_LAUNCH_CHECK();
+            MV_LAUNCH("k_window_eval", k_window_wave, dim3(g), dim3(256), 0, ctx->stream, a, bpp, (int)nblk, masks,
+                      desc0, desc1, num_selected, patches1, qr);
         } else {
         const int bpp = (N + 4 * kQPW - 1) / (4 * kQPW);
         const long nblocks = (long)bpp * batch;
         MV_REQUIRE(nblocks < (1l << 30));
         const unsigned grid = (unsigned)((nblocks + 7) / 8 * 8);
-        MV_PROF_BEGIN(ctx->stream, "k_window_eval");
         if (a.as_built)
-            hipLaunchKernelGGL(k_window_query<true>, dim3(grid), dim3(256), 0, ctx->stream, a, bpp, (int)nblocks,
-                               masks, desc0, desc1, num_selected, patches1, qr);
+            MV_LAUNCH("k_window_eval", k_window_query<true>, dim3(grid), dim3(256), 0, ctx->stream, a, bpp, (int)nblocks,
+                      masks, desc0, desc1, num_selected, patches1, qr);
         else
-            hipLaunchKernelGGL(k_window_query<false>, dim3(grid), dim3(256), 0, ctx->stream, a, bpp, (int)nblocks,
-                               masks, desc0, desc1, num_selected, patches1, qr);
-        MV_PROF_END(ctx->stream);
-        MV_LAUNCH_CHECK();
+            MV_LAUNCH("k_window_eval", k_window_query<false>, dim3(grid), dim3(256), 0, ctx->stream, a, bpp,
+                      (int)nblocks, masks, desc0, desc1, num_selected, patches1, qr);
         }
     } else {
-        MV_PROF_BEGIN(ctx->stream, "k_window_eval");
-        hipLaunchKernelGGL(k_window_eval, dim3((N + 3) / 4, batch), dim3(256), 0, ctx->stream, a, desc0, max_idx0,
-                           probs0, desc1, num_selected, patches1, qr);
-        MV_PROF_END(ctx->stream);
-        MV_LAUNCH_CHECK();
+        MV_LAUNCH("k_window_eval", k_window_eval, dim3((N + 3) / 4, batch), dim3(256), 0, ctx->stream, a, desc0,
+                  max_idx0, probs0, desc1, num_selected, patches1, qr);
     }
-    MV_PROF_BEGIN(ctx->stream, "k_window_compact");
-    hipLaunchKernelGGL(k_window_compact, dim3(batch), dim3(1024), 0, ctx->stream, N, rows, p->max_matches, qr,
-                       num_selected, patches1, indices1, max_idx0, cells, num_matches, points1, points2,
-                       query_of_match);
-    MV_PROF_END(ctx->stream);
-    MV_LAUNCH_CHECK();
+    MV_LAUNCH("k_window_compact", k_window_compact, dim3(batch), dim3(1024), 0, ctx->stream, N, rows, p->max_matches,
+              qr, num_selected, patches1, indices1, max_idx0, cells, num_matches, points1, points2, query_of_match);
     return MV_OK;
 }

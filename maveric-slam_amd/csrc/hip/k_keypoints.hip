@@ -56,40 +56,40 @@ struct KpScratch {
     float *nhwc;        // [B][Hc*Wc][256]
 };
 
-size_t a256(size_t x) { return mv::align_up(x, 256); }
 bool kp_planes_path(int Hc, int Wc) { return (long)Hc * Wc <= KP_PLANE_CELLS; }
 
-size_t kp_scratch_bytes(int B, int Hc, int Wc, int cap) {
+KpScratch kp_scratch_layout(mv::Carve &c, int B, int Hc, int Wc, int cap) {
     const size_t P = (size_t)Hc * Wc * 64;
     const size_t hnc = (size_t)hn_cands((long)P);
-    return a256((size_t)B * P * 4) * 4 + a256((size_t)B * hnc * HN * 4) + a256((size_t)B * hnc * 4) +
-           a256((size_t)B * P) + a256((size_t)B * cap * 4) +
-           (kp_planes_path(Hc, Wc) ? 0 : a256((size_t)B * Hc * Wc * 256 * 4));  // the NHWC copy
+    KpScratch m;
+    m.heat = c.take<float>(B * P);
+    m.hn = c.take<int>(B * hnc * HN);
+    m.hc = c.take<int>(B * hnc);
+    m.cpix = c.take<int>(B * P);
+    m.cconf = c.take<float>(B * P);
+    m.kept = c.take<int>(B * P);
+    m.st = c.take<unsigned char>(B * P);
+    m.slot_pix = c.take<int>((size_t)B * cap);
+    m.nhwc = kp_planes_path(Hc, Wc) ? nullptr : c.take<float>(B * P * 4);  // the NHWC copy: Hc*Wc*256 per frame
+    return m;
 }
 
-KpScratch kp_scratch_map(char *base, int B, int Hc, int Wc, int cap) {
-    const size_t P = (size_t)Hc * Wc * 64;
-    KpScratch m;
-    size_t o = 0;
-    m.heat = (float *)(base + o);
-    o += a256((size_t)B * P * 4);
-    const size_t hnc = (size_t)hn_cands((long)P);
-    m.hn = (int *)(base + o);
-    o += a256((size_t)B * hnc * HN * 4);
-    m.hc = (int *)(base + o);
-    o += a256((size_t)B * hnc * 4);
-    m.cpix = (int *)(base + o);
-    o += a256((size_t)B * P * 4);
-    m.cconf = (float *)(base + o);
-    o += a256((size_t)B * P * 4);
-    m.kept = (int *)(base + o);
-    o += a256((size_t)B * P * 4);
-    m.st = (unsigned char *)(base + o);
-    o += a256((size_t)B * P);
-    m.slot_pix = (int *)(base + o);
-    o += a256((size_t)B * cap * 4);
-    m.nhwc = (float *)(base + o);
-    return m;
+// mv_keypoints_host's staging: one frame in, cap keypoints out
+struct KpStage {
+    float *semi, *desc, *kp, *conf, *out;
+    int *n, *st;
+};
+
+KpStage kp_stage_layout(mv::Carve &c, size_t plane, int cap) {
+    KpStage d;
+    d.semi = c.take<float>(65 * plane);
+    d.desc = c.take<float>(256 * plane);
+    d.kp = c.take<float>((size_t)cap * 2);
+    d.conf = c.take<float>(cap);
+    d.out = c.take<float>((size_t)cap * 256);
+    d.n = c.take<int>(1);
+    d.st = c.take<int>(1);
+    return d;
 }
 
 __global__ __launch_bounds__(256) void k_kp_heat(long cells, int Hc, int Wc, const float *__restrict__ semi,
@@ -751,52 +751,35 @@ extern "C" int mv_keypoints_dev(mv_context *ctx, const mv_kp_params *p, int batc
     MV_REQUIRE((long)Hc * Wc * 64 < (1l << 30) && (long)batch * cap < (1l << 31));
     MV_REQUIRE(((uintptr_t)coarse_desc & 3) == 0 && ((uintptr_t)desc & 15) == 0 && ((uintptr_t)heat & 15) == 0);
     MV_HIP_TRY(hipSetDevice(ctx->device));
-    char *scr = (char *)mv::scratch(ctx, kp_scratch_bytes(batch, Hc, Wc, cap));
-    if (!scr) return MV_ERR_OUT_OF_MEMORY;
-    const KpScratch m = kp_scratch_map(scr, batch, Hc, Wc, cap);
+    mv::Carve scr{(char *)mv::scratch(ctx, mv::carve_bytes(kp_scratch_layout, batch, Hc, Wc, cap))};
+    if (!scr.base) return MV_ERR_OUT_OF_MEMORY;
+    const KpScratch m = kp_scratch_layout(scr, batch, Hc, Wc, cap);
     float *hm = heat ? heat : m.heat;
     hipStream_t s = ctx->stream;
     const long cells = (long)batch * Hc * Wc;
-    MV_PROF_BEGIN(s, "k_kp_heat");
-    hipLaunchKernelGGL(k_kp_heat, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, cells, Hc, Wc, semi, hm);
-    MV_PROF_END(s);
-    MV_LAUNCH_CHECK();
-    MV_PROF_BEGIN(s, "k_kp_nms");
-    hipLaunchKernelGGL(k_kp_nms, dim3((unsigned)batch), dim3(NMS_T), 0, s, Hc * 8, Wc * 8, H, W, p->conf_thresh,
-                       p->nms_dist, p->border, cap, hm, m.hn, m.hc, m.cpix, m.cconf, m.st, m.kept, m.slot_pix, num_kp, kp,
-                       conf, status);
-    MV_PROF_END(s);
-    MV_LAUNCH_CHECK();
+    MV_LAUNCH("k_kp_heat", k_kp_heat, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, cells, Hc, Wc, semi, hm);
+    MV_LAUNCH("k_kp_nms", k_kp_nms, dim3((unsigned)batch), dim3(NMS_T), 0, s, Hc * 8, Wc * 8, H, W, p->conf_thresh,
+              p->nms_dist, p->border, cap, hm, m.hn, m.hc, m.cpix, m.cconf, m.st, m.kept, m.slot_pix, num_kp, kp, conf,
+              status);
     const int HW = Hc * Wc;
     const long waves = (long)batch * cap;
     if (kp_planes_path(Hc, Wc)) {
-        MV_PROF_BEGIN(s, "k_kp_sample_planes");
         if (HW <= KP_PLANE_CELLS_S)
-            hipLaunchKernelGGL((k_kp_sample_planes<KP_CH, KP_PLANE_CELLS_S>),
-                               dim3((unsigned)batch * (256 / KP_CH)), dim3(256), 0, s, batch, cap, Hc, Wc, H, W, Wc * 8,
-                               num_kp, m.slot_pix, coarse_desc, desc);
+            MV_LAUNCH("k_kp_sample_planes", (k_kp_sample_planes<KP_CH, KP_PLANE_CELLS_S>),
+                      dim3((unsigned)batch * (256 / KP_CH)), dim3(256), 0, s, batch, cap, Hc, Wc, H, W, Wc * 8, num_kp,
+                      m.slot_pix, coarse_desc, desc);
         else
-            hipLaunchKernelGGL((k_kp_sample_planes<KP_CH, KP_PLANE_CELLS>), dim3((unsigned)batch * (256 / KP_CH)),
-                               dim3(256), 0, s, batch, cap, Hc, Wc, H, W, Wc * 8, num_kp, m.slot_pix, coarse_desc, desc);
-        MV_PROF_END(s);
-        MV_LAUNCH_CHECK();
-        MV_PROF_BEGIN(s, "k_kp_normalize");
-        hipLaunchKernelGGL(k_kp_normalize, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, batch, cap, num_kp,
-                           desc);
-        MV_PROF_END(s);
-        MV_LAUNCH_CHECK();
+            MV_LAUNCH("k_kp_sample_planes", (k_kp_sample_planes<KP_CH, KP_PLANE_CELLS>),
+                      dim3((unsigned)batch * (256 / KP_CH)), dim3(256), 0, s, batch, cap, Hc, Wc, H, W, Wc * 8, num_kp,
+                      m.slot_pix, coarse_desc, desc);
+        MV_LAUNCH("k_kp_normalize", k_kp_normalize, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, batch, cap,
+                  num_kp, desc);
         return mv::set_status(MV_OK);
     }
-    MV_PROF_BEGIN(s, "k_kp_nhwc");
-    hipLaunchKernelGGL(k_kp_nhwc, dim3((unsigned)((HW + 63) / 64), 4, (unsigned)batch), dim3(256), 0, s, HW,
-                       coarse_desc, m.nhwc);
-    MV_PROF_END(s);
-    MV_LAUNCH_CHECK();
-    MV_PROF_BEGIN(s, "k_kp_sample");
-    hipLaunchKernelGGL(k_kp_sample, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, batch, cap, Hc,
-                       Wc, H, W, Wc * 8, num_kp, m.slot_pix, m.nhwc, desc);
-    MV_PROF_END(s);
-    MV_LAUNCH_CHECK();
+    MV_LAUNCH("k_kp_nhwc", k_kp_nhwc, dim3((unsigned)((HW + 63) / 64), 4, (unsigned)batch), dim3(256), 0, s, HW,
+              coarse_desc, m.nhwc);
+    MV_LAUNCH("k_kp_sample", k_kp_sample, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, batch, cap, Hc, Wc, H, W,
+              Wc * 8, num_kp, m.slot_pix, m.nhwc, desc);
     return mv::set_status(MV_OK);
 }
 
@@ -806,26 +789,22 @@ extern "C" int mv_keypoints_host(mv_context *ctx, const mv_kp_params *p, int Hc,
     MV_REQUIRE(ctx && p && Hc > 0 && Wc > 0 && cap > 0 && semi && coarse_desc && num_kp && kp && conf && desc);
     MV_HIP_TRY(hipSetDevice(ctx->device));
     const size_t plane = (size_t)Hc * Wc;
-    const size_t bs = a256(65 * plane * 4), bd = a256(256 * plane * 4), bk = a256((size_t)cap * 8),
-                 bc = a256((size_t)cap * 4), bo = a256((size_t)cap * 1024);
-    char *d = (char *)mv::stage(ctx, bs + bd + bk + bc + bo + 512);
-    if (!d) return MV_ERR_OUT_OF_MEMORY;
-    float *d_semi = (float *)d, *d_desc = (float *)(d + bs), *d_kp = (float *)(d + bs + bd),
-          *d_conf = (float *)(d + bs + bd + bk), *d_out = (float *)(d + bs + bd + bk + bc);
-    int *d_n = (int *)(d + bs + bd + bk + bc + bo), *d_st = d_n + 64;
+    mv::Carve stg{(char *)mv::stage(ctx, mv::carve_bytes(kp_stage_layout, plane, cap))};
+    if (!stg.base) return MV_ERR_OUT_OF_MEMORY;
+    const KpStage d = kp_stage_layout(stg, plane, cap);
     hipStream_t s = ctx->stream;
-    MV_HIP_TRY(hipMemcpyAsync(d_semi, semi, 65 * plane * 4, hipMemcpyHostToDevice, s));
-    MV_HIP_TRY(hipMemcpyAsync(d_desc, coarse_desc, 256 * plane * 4, hipMemcpyHostToDevice, s));
-    int st = mv_keypoints_dev(ctx, p, 1, Hc, Wc, H, W, d_semi, d_desc, cap, d_n, d_kp, d_conf, d_out, nullptr, d_st);
+    MV_HIP_TRY(hipMemcpyAsync(d.semi, semi, 65 * plane * 4, hipMemcpyHostToDevice, s));
+    MV_HIP_TRY(hipMemcpyAsync(d.desc, coarse_desc, 256 * plane * 4, hipMemcpyHostToDevice, s));
+    int st = mv_keypoints_dev(ctx, p, 1, Hc, Wc, H, W, d.semi, d.desc, cap, d.n, d.kp, d.conf, d.out, nullptr, d.st);
     if (st != MV_OK) return st;
     int n = 0, fst = 0;
-    MV_HIP_TRY(hipMemcpyAsync(&n, d_n, 4, hipMemcpyDeviceToHost, s));
-    MV_HIP_TRY(hipMemcpyAsync(&fst, d_st, 4, hipMemcpyDeviceToHost, s));
+    MV_HIP_TRY(hipMemcpyAsync(&n, d.n, 4, hipMemcpyDeviceToHost, s));
+    MV_HIP_TRY(hipMemcpyAsync(&fst, d.st, 4, hipMemcpyDeviceToHost, s));
     MV_HIP_TRY(hipStreamSynchronize(s));
     if (n > 0) {
-        MV_HIP_TRY(hipMemcpyAsync(kp, d_kp, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-        MV_HIP_TRY(hipMemcpyAsync(conf, d_conf, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-        MV_HIP_TRY(hipMemcpyAsync(desc, d_out, (size_t)n * 1024, hipMemcpyDeviceToHost, s));
+        MV_HIP_TRY(hipMemcpyAsync(kp, d.kp, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+        MV_HIP_TRY(hipMemcpyAsync(conf, d.conf, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+        MV_HIP_TRY(hipMemcpyAsync(desc, d.out, (size_t)n * 1024, hipMemcpyDeviceToHost, s));
         MV_HIP_TRY(hipStreamSynchronize(s));
     }
     *num_kp = n;

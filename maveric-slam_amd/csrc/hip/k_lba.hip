@@ -145,10 +145,7 @@ extern "C" int mv_lba_schur_dev(mv_context *ctx, int batch, int num_poses, int n
     const long lds = 4 * (100 + TL * TL + 2 * S * TL + S * S);
     MV_REQUIRE(lds <= 64 * 1024);
     MV_HIP_TRY(hipSetDevice(ctx->device));
-    MV_PROF_BEGIN(ctx->stream, "k_lba_schur");
-    hipLaunchKernelGGL(k_lba_schur, dim3((unsigned)batch), dim3(256), (size_t)lds, ctx->stream, num_poses, num_ldmks,
-                       chunk, semantics == MV_AS_BUILT ? 1 : 0, J, C);
-    MV_PROF_END(ctx->stream);
-    MV_LAUNCH_CHECK();
+    MV_LAUNCH("k_lba_schur", k_lba_schur, dim3((unsigned)batch), dim3(256), (size_t)lds, ctx->stream, num_poses,
+              num_ldmks, chunk, semantics == MV_AS_BUILT ? 1 : 0, J, C);
     return mv::set_status(MV_OK);
 }

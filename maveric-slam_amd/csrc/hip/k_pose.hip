@@ -183,9 +183,8 @@ int launch_pose(hipStream_t s, void *scratch, const mv_pose_params *p, int batch
     MV_REQUIRE(p && batch > 0 && cap > 0 && n && pts0 && T && num_inliers && status);
     MV_REQUIRE(match_idx ? kp1 != nullptr : pts1 != nullptr);
     if (p->semantics == MV_AS_BUILT) {
-        hipLaunchKernelGGL(k_pose_as_built, dim3(batch), dim3(256), 0, s, cap, n, pts0, pts1, match_idx, kp1,
-                           p->inlier_thresh, T, num_matches, num_inliers, status);
-        MV_LAUNCH_CHECK();
+        MV_LAUNCH(nullptr, k_pose_as_built, dim3(batch), dim3(256), 0, s, cap, n, pts0, pts1, match_idx, kp1,
+                  p->inlier_thresh, T, num_matches, num_inliers, status);
         return MV_OK;
     }
     return launch_intended_pose(s, scratch, p, batch, cap, n, pts0, pts1, match_idx, kp1, T, num_matches,
@@ -194,20 +193,17 @@ int launch_pose(hipStream_t s, void *scratch, const mv_pose_params *p, int batch
 
 int launch_ransac_stub(hipStream_t s, int n, const float *pts1, const float *pts2, float thresh, float *E,
                        int *inliers, int *num_inliers) {
-    hipLaunchKernelGGL(k_ransac_stub, dim3(1), dim3(256), 0, s, n, pts1, pts2, thresh, E, inliers, num_inliers);
-    MV_LAUNCH_CHECK();
+    MV_LAUNCH(nullptr, k_ransac_stub, dim3(1), dim3(256), 0, s, n, pts1, pts2, thresh, E, inliers, num_inliers);
     return MV_OK;
 }
 
 int launch_recover_pose(hipStream_t s, const float *E, float *R1, float *R2, float *t) {
-    hipLaunchKernelGGL(k_recover_pose, dim3(1), dim3(64), 0, s, E, R1, R2, t);
-    MV_LAUNCH_CHECK();
+    MV_LAUNCH(nullptr, k_recover_pose, dim3(1), dim3(64), 0, s, E, R1, R2, t);
     return MV_OK;
 }
 
 int launch_svd3(hipStream_t s, const float *A, float *U, float *S, float *V) {
-    hipLaunchKernelGGL(k_svd3, dim3(1), dim3(64), 0, s, A, U, S, V);
-    MV_LAUNCH_CHECK();
+    MV_LAUNCH(nullptr, k_svd3, dim3(1), dim3(64), 0, s, A, U, S, V);
     return MV_OK;
 }
 

@@ -1073,11 +1073,8 @@ int launch_intended_pose(hipStream_t s, void *scratch, const mv_pose_params *p, 
     a.refine_iters = p->refine_iters;
     a.seed = p->seed;
     const size_t lds = sizeof(float4) * (size_t)(cap < MAXP ? cap : MAXP);
-    MV_PROF_BEGIN(s, "k_pose_ransac");
-    hipLaunchKernelGGL(k_pose_ransac, dim3(batch), dim3(NT), lds, s, a, n, pts0, pts1, match_idx, kp1, T,
-                       num_matches, num_inliers, status);
-    MV_PROF_END(s);
-    MV_LAUNCH_CHECK();
+    MV_LAUNCH("k_pose_ransac", k_pose_ransac, dim3(batch), dim3(NT), lds, s, a, n, pts0, pts1, match_idx, kp1, T,
+              num_matches, num_inliers, status);
     return MV_OK;
 }
 

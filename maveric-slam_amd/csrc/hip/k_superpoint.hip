@@ -899,11 +899,10 @@ int launch_conv(hipStream_t st, const mv_superpoint *net, int li, int B, int H, 
     // the epilogue stores 16 B per lane: NHWC outputs with 16-B aligned pixels
     MV_REQUIRE((OMODE != 0 && !POOL) || (cstride % 16 == 0 && cstride >= 64 * ngroups && ((uintptr_t)out & 15) == 0));
     const char *wd = static_cast<const char *>(net->wdev);
-    hipLaunchKernelGGL((k_sp_conv<CIN, KS, POOL, RELU, OMODE, FUSE1A, GEO>), dim3((unsigned)blocks), dim3(SP_NT), 0, st, in,
-                       H, W, reinterpret_cast<const i32x4 *>(wd + net->frag_off[li]),
-                       reinterpret_cast<const int *>(wd + net->bq_off[li]), net->rs[li], ngroups, tiles_x, tiles_y,
-                       out, cstride, c1);
-    MV_LAUNCH_CHECK();
+    MV_LAUNCH(nullptr, (k_sp_conv<CIN, KS, POOL, RELU, OMODE, FUSE1A, GEO>), dim3((unsigned)blocks), dim3(SP_NT), 0, st,
+              in, H, W, reinterpret_cast<const i32x4 *>(wd + net->frag_off[li]),
+              reinterpret_cast<const int *>(wd + net->bq_off[li]), net->rs[li], ngroups, tiles_x, tiles_y, out, cstride,
+              c1);
     return MV_OK;
 }
 
@@ -923,8 +922,8 @@ int launch_head(hipStream_t st, const mv_superpoint *net, int li, int B, int H, 
     const bool full = HW % 32 == 0 && nblk % HD_NB == 0 && ((uintptr_t)out & 3) == 0;
     const bool fuse = OMODE == 1 && pres && full && nblk_f >= HD_NB;
 #define MV_HEAD(NCB, FULL, PRES)                                                                                   \
-    hipLaunchKernelGGL((k_sp_head<OMODE, NCB, FULL, PRES>), dim3(grid), dim3(SP_NT), 0, st, in, H, W, nblk_f,         \
-                       (int)nblk, wf, bq, net->rs[li], out, cstride, dq, pres)
+    MV_LAUNCH(nullptr, (k_sp_head<OMODE, NCB, FULL, PRES>), dim3(grid), dim3(SP_NT), 0, st, in, H, W, nblk_f,         \
+              (int)nblk, wf, bq, net->rs[li], out, cstride, dq, pres)
     if (cstride == 65) {
         if (fuse)
             MV_HEAD(3, true, OMODE == 1);
@@ -941,7 +940,6 @@ int launch_head(hipStream_t st, const mv_superpoint *net, int li, int B, int H, 
             MV_HEAD(8, false, false);
     }
 #undef MV_HEAD
-    MV_LAUNCH_CHECK();
     if (pres_done) *pres_done = fuse;
     return MV_OK;
 }
@@ -1134,6 +1132,22 @@ int sp_act(mv_superpoint *net, size_t need) {
     net->act_bytes = need;
     return MV_OK;
 }
+
+// activation ping-pong buffers, oh * ow * 16 bytes per frame each (conv1b's pooled output, the
+// largest after the fused conv1a), and with `masks` the presence masks
+struct SpAct {
+    int8_t *A, *Bf;
+    unsigned *pres;
+};
+
+SpAct sp_act_layout(mv::Carve &c, int batch, int oh, int ow, bool masks) {
+    const size_t a = (size_t)batch * oh * ow * 16;
+    SpAct m;
+    m.A = c.take<int8_t>(a);
+    m.Bf = c.take<int8_t>(a);
+    m.pres = masks ? c.take<unsigned>((size_t)batch * 2 * SP_MG_CHUNKS * 8) : nullptr;
+    return m;
+}
 }  // namespace
 
 extern "C" int mv_superpoint_forward_dev(mv_context *ctx, mv_superpoint *net, int batch, int H, int W, int oh,
@@ -1143,32 +1157,27 @@ extern "C" int mv_superpoint_forward_dev(mv_context *ctx, mv_superpoint *net, in
     MV_REQUIRE(images && semi && desc && semi_scale && desc_scale && net->device == ctx->device);
     MV_REQUIRE((long)oh * ow * 64 < (1l << 31) && (long)batch * H * W < (1l << 40));
     MV_HIP_TRY(hipSetDevice(ctx->device));
-    // activation ping-pong buffers, oh * ow * 16 bytes per frame each (conv1b's pooled output, the
-    // largest after the fused conv1a) + the presence masks
-    const size_t a_bytes = mv::align_up((size_t)batch * oh * ow * 16, 256);
-    const size_t need = 2 * a_bytes + (size_t)batch * 2 * SP_MG_CHUNKS * 8 * sizeof(unsigned);
-    int r = sp_act(net, need);
+    int r = sp_act(net, mv::carve_bytes(sp_act_layout, batch, oh, ow, true));
     if (r != MV_OK) return r;
-    int8_t *A = static_cast<int8_t *>(net->act), *Bf = A + a_bytes;
+    mv::Carve act{static_cast<char *>(net->act)};
+    const SpAct m = sp_act_layout(act, batch, oh, ow, true);
     hipStream_t st = ctx->stream;
     // the activations belong to the net, not the context: order this forward after the previous
     // one on whatever stream (context) it ran (free on the same stream)
     if (net->used) MV_HIP_TRY(hipStreamWaitEvent(st, net->done, 0));
-    unsigned *pres = reinterpret_cast<unsigned *>(Bf + a_bytes);
+    unsigned *pres = m.pres;
     bool pres_done = false;
-    if ((r = sp_network(st, net, batch, H, W, oh, ow, images, A, Bf, semi, desc, nullptr, nullptr, pres, &pres_done)) !=
-        MV_OK)
+    if ((r = sp_network(st, net, batch, H, W, oh, ow, images, m.A, m.Bf, semi, desc, nullptr, nullptr, pres,
+                        &pres_done)) != MV_OK)
         return r;
     const int h = oh / 8, w = ow / 8;
     MV_PROF_BEGIN(st, "k_sp_min_gap");
     if (!pres_done) {
-        hipLaunchKernelGGL(k_sp_presence, dim3((unsigned)batch, 2, SP_MG_CHUNKS), dim3(SP_NT), 0, st, semi, desc,
-                           (long)h * w, pres);
-        MV_LAUNCH_CHECK();
+        MV_LAUNCH(nullptr, k_sp_presence, dim3((unsigned)batch, 2, SP_MG_CHUNKS), dim3(SP_NT), 0, st, semi, desc,
+                  (long)h * w, pres);
     }
-    hipLaunchKernelGGL(k_sp_min_gap, dim3((unsigned)batch, 2, SP_MG_CHUNKS), dim3(SP_NT), 0, st, semi, desc,
-                       (long)h * w, net->dq_semi, net->dq_desc, pres, semi_scale, desc_scale);
-    MV_LAUNCH_CHECK();
+    MV_LAUNCH(nullptr, k_sp_min_gap, dim3((unsigned)batch, 2, SP_MG_CHUNKS), dim3(SP_NT), 0, st, semi, desc,
+              (long)h * w, net->dq_semi, net->dq_desc, pres, semi_scale, desc_scale);
     MV_PROF_END(st);
     MV_HIP_TRY(hipEventRecord(net->done, st));
     net->used = true;
@@ -1185,13 +1194,14 @@ extern "C" int mv_superpoint_forward_raw_dev(mv_context *ctx, mv_superpoint *net
     // run()'s network outputs as pairwise_pnp.py receives them (outs = net.forward(inp), :197-199:
     // the quantized model's DeQuantStub): the heads' epilogue writes code * (float) out_scale as
     // NCHW float32 [B][C][oh / 8][ow / 8] directly (no int8 intermediate)
-    const size_t a_bytes = mv::align_up((size_t)batch * oh * ow * 16, 256);
-    int r = sp_act(net, 2 * a_bytes);
+    int r = sp_act(net, mv::carve_bytes(sp_act_layout, batch, oh, ow, false));
     if (r != MV_OK) return r;
-    int8_t *A = static_cast<int8_t *>(net->act), *Bf = A + a_bytes;
+    mv::Carve act{static_cast<char *>(net->act)};
+    const SpAct m = sp_act_layout(act, batch, oh, ow, false);
     hipStream_t st = ctx->stream;
     if (net->used) MV_HIP_TRY(hipStreamWaitEvent(st, net->done, 0));
-    if ((r = sp_network(st, net, batch, H, W, oh, ow, images, A, Bf, nullptr, nullptr, semi, coarse_desc)) != MV_OK)
+    if ((r = sp_network(st, net, batch, H, W, oh, ow, images, m.A, m.Bf, nullptr, nullptr, semi, coarse_desc)) !=
+        MV_OK)
         return r;
     MV_HIP_TRY(hipEventRecord(net->done, st));
     net->used = true;

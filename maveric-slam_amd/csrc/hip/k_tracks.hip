@@ -401,34 +401,24 @@ extern "C" int mv_tracks_link_dev(mv_context *ctx, int batch, int frames, int ca
     MV_REQUIRE(nodes < (1l << 31) && (long)batch * track_cap < (1l << 31));
     MV_HIP_TRY(hipSetDevice(ctx->device));
     const int N = frames * cap, nb = (N + NB - 1) / NB;
-    const size_t b_acc = mv::align_up((size_t)nodes * 4, 256), b_hp = mv::align_up((size_t)nodes, 256);
-    const size_t b_sum = mv::align_up((size_t)batch * nb * 4, 256);
-    char *d = static_cast<char *>(mv::scratch(ctx, 2 * b_acc + b_hp + b_sum));
-    if (!d) return MV_ERR_OUT_OF_MEMORY;
-    int *acc = reinterpret_cast<int *>(d), *rootlen = reinterpret_cast<int *>(d + b_acc);
-    unsigned char *hasprev = reinterpret_cast<unsigned char *>(d + 2 * b_acc);
-    int *blocksum = reinterpret_cast<int *>(d + 2 * b_acc + b_hp);
+    int *acc, *rootlen, *blocksum;
+    unsigned char *hasprev;
+    if (!mv::carve(mv::scratch, ctx, [&](mv::Carve &c) {
+            acc = c.take<int>(nodes);
+            rootlen = c.take<int>(nodes);
+            hasprev = c.take<unsigned char>(nodes);
+            blocksum = c.take<int>((size_t)batch * nb);
+        }))
+        return MV_ERR_OUT_OF_MEMORY;
     hipStream_t s = ctx->stream;
-    MV_PROF_BEGIN(s, "k_tr_claim");
-    hipLaunchKernelGGL(k_tr_claim, dim3((unsigned)(batch * (frames - 1))), dim3(256), (size_t)cap * 8, s, frames, cap, n,
-                       match_idx, match_score, acc, hasprev);
-    MV_PROF_END(s);
-    MV_LAUNCH_CHECK();
-    MV_PROF_BEGIN(s, "k_tr_roots");
-    hipLaunchKernelGGL(k_tr_roots, dim3((unsigned)(batch * nb)), dim3(NB), 0, s, frames, cap, nb, min_len, n, acc,
-                       hasprev, rootlen, blocksum, track_id);
-    MV_PROF_END(s);
-    MV_LAUNCH_CHECK();
-    MV_PROF_BEGIN(s, "k_tr_scan");
-    hipLaunchKernelGGL(k_tr_scan, dim3((unsigned)batch), dim3(256), 0, s, nb, 0, track_cap, blocksum, num_tracks, status,
-                       track_first, track_len);
-    MV_PROF_END(s);
-    MV_LAUNCH_CHECK();
-    MV_PROF_BEGIN(s, "k_tr_number");
-    hipLaunchKernelGGL(k_tr_number, dim3((unsigned)(batch * nb)), dim3(NB), 0, s, frames, cap, nb, track_cap, acc,
-                       rootlen, blocksum, status, track_id, track_first, track_len);
-    MV_PROF_END(s);
-    MV_LAUNCH_CHECK();
+    MV_LAUNCH("k_tr_claim", k_tr_claim, dim3((unsigned)(batch * (frames - 1))), dim3(256), (size_t)cap * 8, s, frames,
+              cap, n, match_idx, match_score, acc, hasprev);
+    MV_LAUNCH("k_tr_roots", k_tr_roots, dim3((unsigned)(batch * nb)), dim3(NB), 0, s, frames, cap, nb, min_len, n, acc,
+              hasprev, rootlen, blocksum, track_id);
+    MV_LAUNCH("k_tr_scan", k_tr_scan, dim3((unsigned)batch), dim3(256), 0, s, nb, 0, track_cap, blocksum, num_tracks,
+              status, track_first, track_len);
+    MV_LAUNCH("k_tr_number", k_tr_number, dim3((unsigned)(batch * nb)), dim3(NB), 0, s, frames, cap, nb, track_cap, acc,
+              rootlen, blocksum, status, track_id, track_first, track_len);
     return mv::set_status(MV_OK);
 }
 
@@ -445,12 +435,9 @@ extern "C" int mv_tracks_triangulate_dev(mv_context *ctx, const mv_landmark_para
     MV_HIP_TRY(hipSetDevice(ctx->device));
     const long total = (long)batch * track_cap;
     hipStream_t s = ctx->stream;
-    MV_PROF_BEGIN(s, "k_tr_triangulate");
-    hipLaunchKernelGGL(k_tr_triangulate, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, s, batch, frames, cap,
-                       track_cap, p->cos_min_parallax, p->min_depth, p->max_reproj_px, poses, cameras, kp, match_idx,
-                       num_tracks, track_first, track_len, status, landmarks, ldmk_flags);
-    MV_PROF_END(s);
-    MV_LAUNCH_CHECK();
+    MV_LAUNCH("k_tr_triangulate", k_tr_triangulate, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, s, batch, frames,
+              cap, track_cap, p->cos_min_parallax, p->min_depth, p->max_reproj_px, poses, cameras, kp, match_idx,
+              num_tracks, track_first, track_len, status, landmarks, ldmk_flags);
     return mv::set_status(MV_OK);
 }
 
@@ -469,20 +456,11 @@ extern "C" int mv_tracks_factors_dev(mv_context *ctx, int batch, int frames, int
     if (!blocksum) return MV_ERR_OUT_OF_MEMORY;
     hipStream_t s = ctx->stream;
     const int N = frames * cap;
-    MV_PROF_BEGIN(s, "k_tr_fcount");
-    hipLaunchKernelGGL(k_tr_fcount, dim3((unsigned)nblk), dim3(NB), 0, s, NT, N, track_cap, track_id, ldmk_flags,
-                       blocksum);
-    MV_PROF_END(s);
-    MV_LAUNCH_CHECK();
-    MV_PROF_BEGIN(s, "k_tr_scan");
-    hipLaunchKernelGGL(k_tr_scan, dim3(1), dim3(256), 0, s, nblk, 1, factor_cap, blocksum, pose_offsets + batch * frames,
-                       status, (int *)nullptr, (int *)nullptr);
-    MV_PROF_END(s);
-    MV_LAUNCH_CHECK();
-    MV_PROF_BEGIN(s, "k_tr_femit");
-    hipLaunchKernelGGL(k_tr_femit, dim3((unsigned)nblk), dim3(NB), 0, s, NT, N, cap, track_cap, factor_cap, kp, track_id,
-                       ldmk_flags, blocksum, ldmk_id, pose_id, meas, pose_offsets);
-    MV_PROF_END(s);
-    MV_LAUNCH_CHECK();
+    MV_LAUNCH("k_tr_fcount", k_tr_fcount, dim3((unsigned)nblk), dim3(NB), 0, s, NT, N, track_cap, track_id, ldmk_flags,
+              blocksum);
+    MV_LAUNCH("k_tr_scan", k_tr_scan, dim3(1), dim3(256), 0, s, nblk, 1, factor_cap, blocksum,
+              pose_offsets + batch * frames, status, (int *)nullptr, (int *)nullptr);
+    MV_LAUNCH("k_tr_femit", k_tr_femit, dim3((unsigned)nblk), dim3(NB), 0, s, NT, N, cap, track_cap, factor_cap, kp,
+              track_id, ldmk_flags, blocksum, ldmk_id, pose_id, meas, pose_offsets);
     return mv::set_status(MV_OK);
 }

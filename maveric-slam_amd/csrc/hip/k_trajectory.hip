@@ -93,10 +93,8 @@ extern "C" int mv_trajectory_chain_dev(mv_context *ctx, int batch, int len, cons
     MV_REQUIRE(mode == MV_CHAIN_AS_BUILT || mode == MV_CHAIN_COMPOSE);
     MV_REQUIRE(batch < (1 << 30));
     MV_HIP_TRY(hipSetDevice(ctx->device));
-    MV_PROF_BEGIN(ctx->stream, "k_chain");
-    hipLaunchKernelGGL(k_chain, dim3((unsigned)batch), dim3(64), 0, ctx->stream, len, rel, present, start, mode, poses);
-    MV_PROF_END(ctx->stream);
-    MV_LAUNCH_CHECK();
+    MV_LAUNCH("k_chain", k_chain, dim3((unsigned)batch), dim3(64), 0, ctx->stream, len, rel, present, start, mode,
+              poses);
     return mv::set_status(MV_OK);
 }
 
@@ -107,9 +105,8 @@ extern "C" int mv_trajectory_rebase_dev(mv_context *ctx, int batch, int len1, co
     MV_HIP_TRY(hipSetDevice(ctx->device));
     const long total = (long)batch * len1;
     MV_REQUIRE(total < (1l << 40));
-    hipLaunchKernelGGL(k_rebase, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, total, len1, base,
-                       mode, poses);
-    MV_LAUNCH_CHECK();
+    MV_LAUNCH(nullptr, k_rebase, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, total, len1, base,
+              mode, poses);
     return mv::set_status(MV_OK);
 }
 
@@ -117,14 +114,15 @@ extern "C" int mv_trajectory_chain_host(mv_context *ctx, int len, const double *
                                         const double *start, int mode, double *poses) {
     MV_REQUIRE(ctx && len >= 0 && (rel || len == 0) && poses);
     MV_HIP_TRY(hipSetDevice(ctx->device));
-    const size_t brel = mv::align_up((size_t)len * 96 + 8, 256), bpres = mv::align_up((size_t)len * 4 + 4, 256);
-    const size_t bst = 256, bout = mv::align_up((size_t)(len + 1) * 96, 256);
-    char *d = (char *)mv::stage(ctx, brel + bpres + bst + bout);
-    if (!d) return MV_ERR_OUT_OF_MEMORY;
-    double *d_rel = (double *)d;
-    int *d_pres = (int *)(d + brel);
-    double *d_start = (double *)(d + brel + bpres);
-    double *d_out = (double *)(d + brel + bpres + bst);
+    double *d_rel, *d_start, *d_out;
+    int *d_pres;
+    if (!mv::carve(mv::stage, ctx, [&](mv::Carve &c) {
+            d_rel = c.take<double>((size_t)len * 12 + 1);
+            d_pres = c.take<int>((size_t)len + 1);
+            d_start = c.take<double>(12);
+            d_out = c.take<double>((size_t)(len + 1) * 12);
+        }))
+        return MV_ERR_OUT_OF_MEMORY;
     hipStream_t s = ctx->stream;
     if (len > 0) MV_HIP_TRY(hipMemcpyAsync(d_rel, rel, (size_t)len * 96, hipMemcpyHostToDevice, s));
     if (present && len > 0) MV_HIP_TRY(hipMemcpyAsync(d_pres, present, (size_t)len * 4, hipMemcpyHostToDevice, s));

@@ -209,11 +209,14 @@ extern "C" int mv_match_two_way_f32_dev(mv_context *ctx, int batch, int cap, con
         if (st != MV_OK) return st;
         scr = ctx->ap_image.p;
     }
-    const size_t nb = mv::align_up((size_t)batch * cap * 4, 256);
-    char *tmp = (char *)mv::scratch(ctx, 2 * nb);
-    if (!tmp) return MV_ERR_OUT_OF_MEMORY;
-    int *ridx = (int *)tmp;
-    float *fdist = match_dist ? match_dist : (float *)(tmp + nb);
+    int *ridx;
+    float *tdist;  // the distances, when the caller keeps none
+    if (!mv::carve(mv::scratch, ctx, [&](mv::Carve &c) {
+            ridx = c.take<int>((size_t)batch * cap);
+            tdist = c.take<float>((size_t)batch * cap);
+        }))
+        return MV_ERR_OUT_OF_MEMORY;
+    float *fdist = match_dist ? match_dist : tdist;
     hipStream_t s = ctx->stream;
     // forward: rows of frame 0 against frame 1 (argmin distance + its exact distance)
     int st = sc == MV_SCREEN_I8 ? MV_OK : ap_prepare(sc, s, scr, batch, cap, n1, desc1);
@@ -223,9 +226,8 @@ extern "C" int mv_match_two_way_f32_dev(mv_context *ctx, int batch, int cap, con
     if (st == MV_OK) st = ap_match(ctx, sc, s, scr, batch, cap, n1, n0, desc1, desc0, 0.0, ridx, nullptr, 1);
     if (st != MV_OK) return st;
     const long total = (long)batch * cap;
-    hipLaunchKernelGGL(k_two_way_keep, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, total, cap, n0, n1,
-                       ridx, (float)nn_thresh, match_idx, fdist, match_dist ? 1 : 0);
-    MV_LAUNCH_CHECK();
+    MV_LAUNCH(nullptr, k_two_way_keep, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, total, cap, n0, n1, ridx,
+              (float)nn_thresh, match_idx, fdist, match_dist ? 1 : 0);
     return mv::set_status(MV_OK);
 }
 

@@ -1,28 +1,10 @@
 // mv_api.hip -- extern "C" entry points of libmaveric_hip.so that are not a
 // single kernel launcher: parameter defaults, host-pointer (one frame / one
-// pair) wrappers, batched pose, and the whole-pair tracking call.
+// pair) wrappers -- each carves its device copies out of the context staging
+// buffer (mv::carve) --, batched pose, and the whole-pair tracking call.
 #include <string.h>
 
 #include "mv_internal.hpp"
-
-namespace {
-
-// bump allocator over the context staging buffer (host-pointer calls only)
-struct Bump {
-    char *base;
-    size_t off;
-    template <class T>
-    T *take(size_t count) {
-        off = mv::align_up(off, 256);
-        T *p = reinterpret_cast<T *>(base + off);
-        off += sizeof(T) * count;
-        return p;
-    }
-};
-
-size_t a256(size_t b) { return mv::align_up(b, 256); }
-
-}  // namespace
 
 extern "C" {
 
@@ -93,14 +75,17 @@ int mv_softmax_host(mv_context *ctx, float scale, const int8_t *semi, int cells,
                     float *probs) {
     MV_REQUIRE(ctx && semi && cells > 0 && num_valid && max_indices && probs);
     MV_HIP_TRY(hipSetDevice(ctx->device));
-    const size_t need = a256(4) + a256((size_t)cells * 65) + 2 * a256((size_t)cells * 4) + a256(4) + 4096;
-    Bump bp{(char *)mv::stage(ctx, need), 0};
-    if (!bp.base) return MV_ERR_OUT_OF_MEMORY;
-    float *d_scale = bp.take<float>(1);
-    int8_t *d_semi = bp.take<int8_t>((size_t)cells * 65);
-    int *d_mi = bp.take<int>(cells);
-    float *d_pr = bp.take<float>(cells);
-    int *d_nv = bp.take<int>(1);
+    float *d_scale, *d_pr;
+    int8_t *d_semi;
+    int *d_mi, *d_nv;
+    if (!mv::carve(mv::stage, ctx, [&](mv::Carve &c) {
+            d_scale = c.take<float>(1);
+            d_semi = c.take<int8_t>((size_t)cells * 65);
+            d_mi = c.take<int>(cells);
+            d_pr = c.take<float>(cells);
+            d_nv = c.take<int>(1);
+        }))
+        return MV_ERR_OUT_OF_MEMORY;
     hipStream_t s = ctx->stream;
     MV_HIP_TRY(hipMemcpyAsync(d_scale, &scale, 4, hipMemcpyHostToDevice, s));
     MV_HIP_TRY(hipMemcpyAsync(d_semi, semi, (size_t)cells * 65, hipMemcpyHostToDevice, s));
@@ -119,20 +104,22 @@ int mv_top_n_host(mv_context *ctx, float scale, const int8_t *semi, int cells, i
                   int *patches, int *indices, float *probs) {
     MV_REQUIRE(ctx && semi && cells > 0 && N > 0 && cap > 0 && num_selected && patches && indices && probs);
     MV_HIP_TRY(hipSetDevice(ctx->device));
-    const size_t need = a256(4) + a256((size_t)cells * 65) + 2 * a256((size_t)cells * 4) + 4 * a256(4) +
-                        2 * a256((size_t)N * 4) + a256((size_t)N * 4) + 4096;
-    Bump bp{(char *)mv::stage(ctx, need), 0};
-    if (!bp.base) return MV_ERR_OUT_OF_MEMORY;
-    float *d_scale = bp.take<float>(1);
-    int8_t *d_semi = bp.take<int8_t>((size_t)cells * 65);
-    int *d_mi = bp.take<int>(cells);
-    float *d_pr = bp.take<float>(cells);
-    int *d_nv = bp.take<int>(1);
-    int *d_ns = bp.take<int>(1);
-    int *d_st = bp.take<int>(1);
-    int *d_pa = bp.take<int>(N);
-    int *d_ix = bp.take<int>(N);
-    float *d_sp = bp.take<float>(N);
+    float *d_scale, *d_pr, *d_sp;
+    int8_t *d_semi;
+    int *d_mi, *d_nv, *d_ns, *d_st, *d_pa, *d_ix;
+    if (!mv::carve(mv::stage, ctx, [&](mv::Carve &c) {
+            d_scale = c.take<float>(1);
+            d_semi = c.take<int8_t>((size_t)cells * 65);
+            d_mi = c.take<int>(cells);
+            d_pr = c.take<float>(cells);
+            d_nv = c.take<int>(1);
+            d_ns = c.take<int>(1);
+            d_st = c.take<int>(1);
+            d_pa = c.take<int>(N);
+            d_ix = c.take<int>(N);
+            d_sp = c.take<float>(N);
+        }))
+        return MV_ERR_OUT_OF_MEMORY;
     hipStream_t s = ctx->stream;
     MV_HIP_TRY(hipMemcpyAsync(d_scale, &scale, 4, hipMemcpyHostToDevice, s));
     MV_HIP_TRY(hipMemcpyAsync(d_semi, semi, (size_t)cells * 65, hipMemcpyHostToDevice, s));
@@ -165,21 +152,23 @@ int mv_window_match_host(mv_context *ctx, const mv_window_params *p, int rows, i
     MV_REQUIRE(num_queries == 0 || (patches1 && indices1));
     MV_HIP_TRY(hipSetDevice(ctx->device));
     const int cells = rows * cols, N = num_queries > 0 ? num_queries : 1, M = p->max_matches;
-    const size_t need = 2 * a256((size_t)cells * 256) + 2 * a256((size_t)cells * 4) + 3 * a256((size_t)N * 4) +
-                        2 * a256((size_t)M * 8) + a256((size_t)M * 4) + a256(4) + 4096;
-    Bump bp{(char *)mv::stage(ctx, need), 0};
-    if (!bp.base) return MV_ERR_OUT_OF_MEMORY;
-    int8_t *d_d0 = bp.take<int8_t>((size_t)cells * 256);
-    int8_t *d_d1 = bp.take<int8_t>((size_t)cells * 256);
-    int *d_mi = bp.take<int>(cells);
-    float *d_pr = bp.take<float>(cells);
-    int *d_ns = bp.take<int>(1);
-    int *d_pa = bp.take<int>(N);
-    int *d_ix = bp.take<int>(N);
-    int *d_nm = bp.take<int>(1);
-    float *d_p1 = bp.take<float>((size_t)M * 2);
-    float *d_p2 = bp.take<float>((size_t)M * 2);
-    int *d_q = bp.take<int>(M);
+    int8_t *d_d0, *d_d1;
+    int *d_mi, *d_ns, *d_pa, *d_ix, *d_nm, *d_q;
+    float *d_pr, *d_p1, *d_p2;
+    if (!mv::carve(mv::stage, ctx, [&](mv::Carve &c) {
+            d_d0 = c.take<int8_t>((size_t)cells * 256);
+            d_d1 = c.take<int8_t>((size_t)cells * 256);
+            d_mi = c.take<int>(cells);
+            d_pr = c.take<float>(cells);
+            d_ns = c.take<int>(1);
+            d_pa = c.take<int>(N);
+            d_ix = c.take<int>(N);
+            d_nm = c.take<int>(1);
+            d_p1 = c.take<float>((size_t)M * 2);
+            d_p2 = c.take<float>((size_t)M * 2);
+            d_q = c.take<int>(M);
+        }))
+        return MV_ERR_OUT_OF_MEMORY;
     hipStream_t s = ctx->stream;
     MV_HIP_TRY(hipMemcpyAsync(d_d0, desc0, (size_t)cells * 256, hipMemcpyHostToDevice, s));
     MV_HIP_TRY(hipMemcpyAsync(d_d1, desc1, (size_t)cells * 256, hipMemcpyHostToDevice, s));
@@ -231,14 +220,16 @@ int mv_ransac_stub_host(mv_context *ctx, int n, const float *pts1, const float *
                         int *best_inliers, int *num_inliers) {
     MV_REQUIRE(ctx && n > 0 && pts1 && pts2 && best_E && best_inliers && num_inliers);
     MV_HIP_TRY(hipSetDevice(ctx->device));
-    const size_t need = 2 * a256((size_t)n * 8) + a256(36) + a256(1000 * 4) + a256(4) + 4096;
-    Bump bp{(char *)mv::stage(ctx, need), 0};
-    if (!bp.base) return MV_ERR_OUT_OF_MEMORY;
-    float *d_p1 = bp.take<float>((size_t)n * 2);
-    float *d_p2 = bp.take<float>((size_t)n * 2);
-    float *d_E = bp.take<float>(9);
-    int *d_in = bp.take<int>(1000);
-    int *d_n = bp.take<int>(1);
+    float *d_p1, *d_p2, *d_E;
+    int *d_in, *d_n;
+    if (!mv::carve(mv::stage, ctx, [&](mv::Carve &c) {
+            d_p1 = c.take<float>((size_t)n * 2);
+            d_p2 = c.take<float>((size_t)n * 2);
+            d_E = c.take<float>(9);
+            d_in = c.take<int>(1000);
+            d_n = c.take<int>(1);
+        }))
+        return MV_ERR_OUT_OF_MEMORY;
     hipStream_t s = ctx->stream;
     MV_HIP_TRY(hipMemcpyAsync(d_p1, pts1, (size_t)n * 8, hipMemcpyHostToDevice, s));
     MV_HIP_TRY(hipMemcpyAsync(d_p2, pts2, (size_t)n * 8, hipMemcpyHostToDevice, s));
@@ -259,12 +250,14 @@ int mv_ransac_stub_host(mv_context *ctx, int n, const float *pts1, const float *
 static int small_call(mv_context *ctx, int which, const float *in, float *o1, float *o2, float *o3) {
     MV_REQUIRE(ctx && in && o1 && o2 && o3);
     MV_HIP_TRY(hipSetDevice(ctx->device));
-    Bump bp{(char *)mv::stage(ctx, 4096), 0};
-    if (!bp.base) return MV_ERR_OUT_OF_MEMORY;
-    float *d_in = bp.take<float>(9);
-    float *d_1 = bp.take<float>(9);
-    float *d_2 = bp.take<float>(9);
-    float *d_3 = bp.take<float>(9);
+    float *d_in, *d_1, *d_2, *d_3;
+    if (!mv::carve(mv::stage, ctx, [&](mv::Carve &c) {
+            d_in = c.take<float>(9);
+            d_1 = c.take<float>(9);
+            d_2 = c.take<float>(9);
+            d_3 = c.take<float>(9);
+        }))
+        return MV_ERR_OUT_OF_MEMORY;
     hipStream_t s = ctx->stream;
     MV_HIP_TRY(hipMemcpyAsync(d_in, in, 36, hipMemcpyHostToDevice, s));
     int st = which == 0 ? mv::launch_recover_pose(s, d_in, d_1, d_2, d_3) : mv::launch_svd3(s, d_in, d_1, d_2, d_3);
@@ -291,32 +284,33 @@ int mv_track_pair_host(mv_context *ctx, const mv_track_params *p, int rows, int 
     MV_REQUIRE(points1 && points2 && p->top_n > 0 && p->window.max_matches > 0);
     MV_HIP_TRY(hipSetDevice(ctx->device));
     const int cells = rows * cols, N = p->top_n, M = p->window.max_matches;
-    const size_t need = 2 * a256(8) + 2 * a256((size_t)cells * 65) + 2 * a256((size_t)cells * 256) +
-                        4 * a256((size_t)cells * 4) + 8 * a256(4) + 3 * a256((size_t)N * 4) +
-                        2 * a256((size_t)M * 8) + a256(48) + 8192;
-    Bump bp{(char *)mv::stage(ctx, need), 0};
-    if (!bp.base) return MV_ERR_OUT_OF_MEMORY;
-    float *d_sc = bp.take<float>(2);
-    int8_t *d_s0 = bp.take<int8_t>((size_t)cells * 65);
-    int8_t *d_s1 = bp.take<int8_t>((size_t)cells * 65);
-    int8_t *d_d0 = bp.take<int8_t>((size_t)cells * 256);
-    int8_t *d_d1 = bp.take<int8_t>((size_t)cells * 256);
-    int *d_mi0 = bp.take<int>(cells);
-    float *d_pr0 = bp.take<float>(cells);
-    int *d_mi1 = bp.take<int>(cells);
-    float *d_pr1 = bp.take<float>(cells);
-    int *d_nv = bp.take<int>(2);
-    int *d_ns = bp.take<int>(1);
-    int *d_st = bp.take<int>(1);
-    int *d_pa = bp.take<int>(N);
-    int *d_ix = bp.take<int>(N);
-    float *d_sp = bp.take<float>(N);
-    int *d_nm = bp.take<int>(1);
-    float *d_p1 = bp.take<float>((size_t)M * 2);
-    float *d_p2 = bp.take<float>((size_t)M * 2);
-    float *d_T = bp.take<float>(12);
-    int *d_ni = bp.take<int>(1);
-    int *d_ps = bp.take<int>(1);
+    float *d_sc, *d_pr0, *d_pr1, *d_sp, *d_p1, *d_p2, *d_T;
+    int8_t *d_s0, *d_s1, *d_d0, *d_d1;
+    int *d_mi0, *d_mi1, *d_nv, *d_ns, *d_st, *d_pa, *d_ix, *d_nm, *d_ni, *d_ps;
+    if (!mv::carve(mv::stage, ctx, [&](mv::Carve &c) {
+            d_sc = c.take<float>(2);
+            d_s0 = c.take<int8_t>((size_t)cells * 65);
+            d_s1 = c.take<int8_t>((size_t)cells * 65);
+            d_d0 = c.take<int8_t>((size_t)cells * 256);
+            d_d1 = c.take<int8_t>((size_t)cells * 256);
+            d_mi0 = c.take<int>(cells);
+            d_pr0 = c.take<float>(cells);
+            d_mi1 = c.take<int>(cells);
+            d_pr1 = c.take<float>(cells);
+            d_nv = c.take<int>(2);
+            d_ns = c.take<int>(1);
+            d_st = c.take<int>(1);
+            d_pa = c.take<int>(N);
+            d_ix = c.take<int>(N);
+            d_sp = c.take<float>(N);
+            d_nm = c.take<int>(1);
+            d_p1 = c.take<float>((size_t)M * 2);
+            d_p2 = c.take<float>((size_t)M * 2);
+            d_T = c.take<float>(12);
+            d_ni = c.take<int>(1);
+            d_ps = c.take<int>(1);
+        }))
+        return MV_ERR_OUT_OF_MEMORY;
     hipStream_t s = ctx->stream;
     const bool built = p->window.semantics == MV_AS_BUILT;
     float sc[2] = {built ? mv_scale_as_built(semi_scale0) : semi_scale0,

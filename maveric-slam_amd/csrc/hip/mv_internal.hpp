@@ -5,6 +5,7 @@
 #include <stddef.h>
 
 #include "maveric_hip.h"
+#include "mv_carve.hpp"
 
 // A grow-only device buffer of a context (mv::grow)
 struct mv_buffer {
@@ -74,8 +75,17 @@ int grow(mv_context *ctx, mv_buffer &b, size_t bytes, const char *what);
 // the context scratch / staging buffer of at least `bytes`; nullptr on failure
 void *scratch(mv_context *ctx, size_t bytes);
 void *stage(mv_context *ctx, size_t bytes);
-
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+// Carve `layout` (a callable on a Carve &, written once) out of the context scratch / staging
+// buffer: a measuring pass sizes the buffer, a second pass on its base places the arrays.
+// false: the buffer could not be had (out of memory)
+template <class F>
+bool carve(void *(*buffer)(mv_context *, size_t), mv_context *ctx, F layout) {
+    Carve need{nullptr};
+    layout(need);
+    Carve c{static_cast<char *>(buffer(ctx, need.bytes()))};
+    if (c.base) layout(c);
+    return c.base != nullptr;
+}
 
 // Wait for every stream this context has issued work on (its own stream -- which waits on every
 // stream the context left, via ev_retire --, the current stream and the staging stream) -- before
@@ -112,7 +122,17 @@ void prof_end(hipStream_t s);
         }                                                                                  \
     } while (0)
 
-#define MV_LAUNCH_CHECK() MV_HIP_TRY(hipGetLastError())
+// The one launch form: the profiler bracket under `name` (nullptr: none), the launch, and the
+// launch check, which returns MV_ERR_HIP from the enclosing function with the launch site's
+// file:line.  A template kernel goes in parentheses, as for hipLaunchKernelGGL.
+#define MV_LAUNCH(name, kernel, grid, block, lds_bytes, stream, ...)                       \
+    do {                                                                                   \
+        const char *_name = (name);                                                        \
+        if (_name) MV_PROF_BEGIN((stream), _name);                                         \
+        hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, __VA_ARGS__);           \
+        if (_name) MV_PROF_END(stream);                                                    \
+        MV_HIP_TRY(hipGetLastError());                                                     \
+    } while (0)
 
 #define MV_REQUIRE(cond)                                                                   \
     do {                                                                                   \
