@@ -8,19 +8,9 @@
 //                    local_bundle_adjustment.c), the J rows of 8 factors loaded ahead.
 #include "factors.h"
 #include "mv_internal.hpp"
+#include "pf_linearize.hpp"
 
 namespace {
-
-__device__ __forceinline__ void qmul(const float *a, const float *b, float *o) {  // types.c:19-26 order
-    o[0] = __fsub_rn(__fsub_rn(__fsub_rn(__fmul_rn(a[0], b[0]), __fmul_rn(a[1], b[1])), __fmul_rn(a[2], b[2])),
-                     __fmul_rn(a[3], b[3]));
-    o[1] = __fsub_rn(__fadd_rn(__fadd_rn(__fmul_rn(a[0], b[1]), __fmul_rn(a[1], b[0])), __fmul_rn(a[2], b[3])),
-                     __fmul_rn(a[3], b[2]));
-    o[2] = __fadd_rn(__fadd_rn(__fsub_rn(__fmul_rn(a[0], b[2]), __fmul_rn(a[1], b[3])), __fmul_rn(a[2], b[0])),
-                     __fmul_rn(a[3], b[1]));
-    o[3] = __fadd_rn(__fsub_rn(__fadd_rn(__fmul_rn(a[0], b[3]), __fmul_rn(a[1], b[2])), __fmul_rn(a[2], b[1])),
-                     __fmul_rn(a[3], b[0]));
-}
 
 __global__ __launch_bounds__(256) void k_pf_linearize(int F, const float *__restrict__ ldmk,
                                                       const float *__restrict__ pose, const float *__restrict__ cam,
@@ -30,49 +20,11 @@ __global__ __launch_bounds__(256) void k_pf_linearize(int F, const float *__rest
     const int f = blockIdx.x * 256 + threadIdx.x;
     if (f >= F) return;
     const float *X = ldmk + 3l * lid[f], *T = pose + 7l * pid[f], *K = cam + 4l * pid[f];
-    const float vq[4] = {0.f, X[0], X[1], X[2]}, qc[4] = {T[0], -T[1], -T[2], -T[3]};
-    float qv[4], r[4];
-    qmul(T, vq, qv);
-    qmul(qv, qc, r);
-    const float px = __fadd_rn(r[1], __fmul_rn(1.f, T[4])), py = __fadd_rn(r[2], __fmul_rn(1.f, T[5])),
-                pz = __fadd_rn(r[3], __fmul_rn(1.f, T[6]));
-    const float ux = px / pz, uy = py / pz;
-    const float ex = __fadd_rn(__fadd_rn(__fmul_rn(ux, K[0]), K[2]), __fmul_rn(-1.f, meas[2l * f]));
-    const float ey = __fadd_rn(__fadd_rn(__fmul_rn(uy, K[1]), K[3]), __fmul_rn(-1.f, meas[2l * f + 1]));
-    err[2l * f] = ex;
-    err[2l * f + 1] = ey;
-    if (!Jout && !Hout) return;
-    const float iz = 1.f / pz;
-    const float d00 = __fmul_rn(K[0], iz), d02 = __fmul_rn(__fmul_rn(-__fmul_rn(K[0], px), iz), iz);
-    const float d11 = __fmul_rn(K[1], iz), d12 = __fmul_rn(__fmul_rn(-__fmul_rn(K[1], py), iz), iz);
-    const float w = T[0], x = T[1], y = T[2], z = T[3];
-    const float ww = __fmul_rn(w, w), xx = __fmul_rn(x, x), yy = __fmul_rn(y, y), zz = __fmul_rn(z, z);
-    const float R[9] = {__fsub_rn(__fsub_rn(__fadd_rn(ww, xx), yy), zz),
-                        __fmul_rn(2.f, __fsub_rn(__fmul_rn(x, y), __fmul_rn(w, z))),
-                        __fmul_rn(2.f, __fadd_rn(__fmul_rn(x, z), __fmul_rn(w, y))),
-                        __fmul_rn(2.f, __fadd_rn(__fmul_rn(x, y), __fmul_rn(w, z))),
-                        __fsub_rn(__fadd_rn(__fsub_rn(ww, xx), yy), zz),
-                        __fmul_rn(2.f, __fsub_rn(__fmul_rn(y, z), __fmul_rn(w, x))),
-                        __fmul_rn(2.f, __fsub_rn(__fmul_rn(x, z), __fmul_rn(w, y))),
-                        __fmul_rn(2.f, __fadd_rn(__fmul_rn(y, z), __fmul_rn(w, x))),
-                        __fadd_rn(__fsub_rn(__fsub_rn(ww, xx), yy), zz)};
-    const float S[9] = {0.f, pz, -py, -pz, 0.f, px, py, -px, 0.f};
     float J[20];
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        J[2 * c] = __fadd_rn(__fmul_rn(d00, R[c]), __fmul_rn(d02, R[6 + c]));
-        J[2 * c + 1] = __fadd_rn(__fmul_rn(d11, R[3 + c]), __fmul_rn(d12, R[6 + c]));
-        J[2 * (3 + c)] = __fadd_rn(__fmul_rn(d00, S[c]), __fmul_rn(d02, S[6 + c]));
-        J[2 * (3 + c) + 1] = __fadd_rn(__fmul_rn(d11, S[3 + c]), __fmul_rn(d12, S[6 + c]));
-    }
-    J[12] = d00;
-    J[13] = 0.f;
-    J[14] = 0.f;
-    J[15] = d11;
-    J[16] = d02;
-    J[17] = d12;
-    J[18] = ex;
-    J[19] = ey;
+    mv::pf_linearize(X, T, K, meas[2l * f], meas[2l * f + 1], Jout || Hout, J);
+    err[2l * f] = J[18];
+    err[2l * f + 1] = J[19];
+    if (!Jout && !Hout) return;
     if (Jout) {
         float4 *o = reinterpret_cast<float4 *>(Jout + 20l * f);
 #pragma unroll

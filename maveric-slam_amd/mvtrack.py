@@ -74,6 +74,13 @@ class LandmarkParams(ctypes.Structure):
     _fields_ = [("cos_min_parallax", _D), ("min_depth", _D), ("max_reproj_px", _D)]
 
 
+class BaParams(ctypes.Structure):
+    """mv_ba_params (include/bundle_adjust.h)."""
+    _fields_ = [("max_iters", _I), ("lambda_init", _D), ("lambda_up", _D), ("lambda_down", _D), ("lambda_min", _D),
+                ("lambda_max", _D), ("diag_floor", _D), ("rel_tol", _D), ("huber_px", _D)]
+
+
+BA_MAX_POSES = 16  # MV_BA_MAX_POSES
 LDMK_LOW_PARALLAX, LDMK_BEHIND, LDMK_REPROJ, LDMK_DEGENERATE = 1, 2, 4, 8
 TRACKS_MAX_CAP = 8192  # MV_TRACKS_MAX_CAP
 
@@ -197,6 +204,8 @@ def lib():
             "mv_tracks_link_dev": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
             "mv_tracks_triangulate_dev": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
             "mv_tracks_factors_dev": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+            "mv_ba_params_default": (None, [_P]),
+            "mv_ba_solve_dev": (_I, [_P, _P, _I, _I, _I, _I] + [_P] * 14),
         }
         for name, (res, args) in sig.items():
             try:
@@ -428,6 +437,16 @@ def landmark_params(**kw):
     """mv_landmark_params (cos_min_parallax cos(1 degree), min_depth 0.1, max_reproj_px 2)."""
     p = LandmarkParams()
     lib().mv_landmark_params_default(ctypes.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def ba_params(**kw):
+    """mv_ba_params with its defaults (max_iters 10, lambda_init 1e-4, up 10, down 0.1, min 1e-10,
+    max 1e10, diag_floor 1e-6, rel_tol 1e-6, huber_px 0)."""
+    p = BaParams()
+    lib().mv_ba_params_default(ctypes.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     return p
@@ -792,6 +811,22 @@ class Context:
         check(lib().mv_tracks_factors_dev(self.h, B, F, cap, ldmk_flags.shape[1], ldmk_id.shape[0], _t(kp),
                                           _t(track_id), _t(ldmk_flags), _t(ldmk_id), _t(pose_id), _t(meas),
                                           _t(pose_offsets), _t(status)), "tracks_factors")
+
+    # ---------------- windowed bundle adjustment (include/bundle_adjust.h) ----------------
+    ba_params = staticmethod(ba_params)
+
+    def ba_solve(self, poses, landmarks, cameras, ldmk_id, pose_id, meas, pose_offsets, track_cap, poses_out,
+                 landmarks_out, cost_initial, cost_final, iters, status, pose_fixed=None, params=None):
+        """Device tensors: poses [B, F, 7], landmarks [B, track_cap, 3], cameras [B, F, 4] and
+        tracks_factors' outputs (ldmk_id / pose_id [stored], meas [stored, 2], pose_offsets [B * F + 1])
+        -> poses_out, landmarks_out (may be the inputs themselves), cost_initial / cost_final [B]
+        float64, iters / status [B] int32.  pose_fixed [B, F] int32 (None: pose 0 of every window)."""
+        B, F = poses.shape[0], poses.shape[1]
+        p = params or ba_params()
+        check(lib().mv_ba_solve_dev(self.h, ctypes.byref(p), B, F, int(track_cap), ldmk_id.shape[0], _t(poses),
+                                    _t(landmarks), _t(cameras), _t(ldmk_id), _t(pose_id), _t(meas), _t(pose_offsets),
+                                    _t(pose_fixed), _t(poses_out), _t(landmarks_out), _t(cost_initial),
+                                    _t(cost_final), _t(iters), _t(status)), "ba_solve")
 
     # ---------------- loop closure (include/loop_closure.h) ----------------
     def bow_words(self, voc, desc_scales, desc, num_sel, patches, base, wid, word_id, best_match, scores=None):
