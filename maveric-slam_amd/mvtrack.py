@@ -80,7 +80,15 @@ class BaParams(ctypes.Structure):
                 ("lambda_max", _D), ("diag_floor", _D), ("rel_tol", _D), ("huber_px", _D)]
 
 
+class PgParams(ctypes.Structure):
+    """mv_pg_params (include/pose_graph.h)."""
+    _fields_ = [("max_iters", _I), ("lambda_init", _D), ("lambda_up", _D), ("lambda_down", _D), ("lambda_min", _D),
+                ("lambda_max", _D), ("diag_floor", _D), ("rel_tol", _D), ("huber", _D)]
+
+
 BA_MAX_POSES = 16  # MV_BA_MAX_POSES
+PG_MAX_NODES = 512  # MV_PG_MAX_NODES
+PG_EDGE_SE3, PG_EDGE_DIRECTION = 0, 1
 LDMK_LOW_PARALLAX, LDMK_BEHIND, LDMK_REPROJ, LDMK_DEGENERATE = 1, 2, 4, 8
 TRACKS_MAX_CAP = 8192  # MV_TRACKS_MAX_CAP
 
@@ -206,6 +214,10 @@ def lib():
             "mv_tracks_factors_dev": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
             "mv_ba_params_default": (None, [_P]),
             "mv_ba_solve_dev": (_I, [_P, _P, _I, _I, _I, _I] + [_P] * 14),
+            "mv_pg_params_default": (None, [_P]),
+            "mv_pg_solve_dev": (_I, [_P, _P, _I, _I, _I, _I] + [_P] * 13),
+            "mv_pg_envelope_host": (_I, [_I, _I, _P, _P, _P]),
+            "mv_pg_edges_from_transforms_dev": (_I, [_P, _I, _P, _P]),
         }
         for name, (res, args) in sig.items():
             try:
@@ -450,6 +462,30 @@ def ba_params(**kw):
     for k, v in kw.items():
         setattr(p, k, v)
     return p
+
+
+def pg_params(**kw):
+    """mv_pg_params with its defaults (max_iters 10, lambda_init 1e-4, up 10, down 0.1, min 1e-10,
+    max 1e10, diag_floor 1e-6, rel_tol 1e-6, huber 0)."""
+    p = PgParams()
+    lib().mv_pg_params_default(ctypes.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def pg_envelope(nodes, edge_i, edge_j, node_fixed=None):
+    """The row envelope of one pose graph in 6 x 6 blocks (mv_pg_envelope_host), to size pg_solve's
+    env_cap: edge_i / edge_j with local node ids in [0, nodes), node_fixed [nodes] (None: node 0 is
+    held).  Host, no device; raises MVError for an id outside the graph or i == j."""
+    ei, ej = np.ascontiguousarray(edge_i, np.int32), np.ascontiguousarray(edge_j, np.int32)
+    assert ei.shape == ej.shape and ei.ndim == 1
+    fx = None if node_fixed is None else np.ascontiguousarray(node_fixed, np.int32)
+    assert fx is None or fx.shape == (int(nodes),)
+    r = lib().mv_pg_envelope_host(int(nodes), ei.shape[0], _np(ei), _np(ej), None if fx is None else _np(fx))
+    if r < 0:
+        raise MVError("pg_envelope: %s" % lib().mv_status_string(r).decode())
+    return r
 
 
 def poses_to_q7(poses12):
@@ -827,6 +863,29 @@ class Context:
                                     _t(landmarks), _t(cameras), _t(ldmk_id), _t(pose_id), _t(meas), _t(pose_offsets),
                                     _t(pose_fixed), _t(poses_out), _t(landmarks_out), _t(cost_initial),
                                     _t(cost_final), _t(iters), _t(status)), "ba_solve")
+
+    # ---------------- pose-graph optimisation (include/pose_graph.h) ----------------
+    pg_params = staticmethod(pg_params)
+
+    def pg_solve(self, poses, edge_offsets, edge_i, edge_j, edge_kind, edge_z, edge_w, env_cap, poses_out,
+                 cost_initial, cost_final, iters, status, node_fixed=None, params=None):
+        """Device tensors: poses [B, N, 7] float32, edge_offsets [B + 1] int32, edge_i / edge_j /
+        edge_kind [stored] int32 (global node ids g * N + n; PG_EDGE_SE3 or PG_EDGE_DIRECTION), edge_z
+        [stored, 7] float32 (the measured T_j T_i^-1), edge_w [stored, 2] float32 (w_rot, w_trans) ->
+        poses_out (may be poses itself), cost_initial / cost_final [B] float64, iters / status [B]
+        int32.  env_cap: the largest envelope of a graph in blocks (pg_envelope).  node_fixed [B, N]
+        int32 (None: node 0 of every graph)."""
+        B, N = poses.shape[0], poses.shape[1]
+        p = params or pg_params()
+        check(lib().mv_pg_solve_dev(self.h, ctypes.byref(p), B, N, edge_i.shape[0], int(env_cap), _t(poses),
+                                    _t(edge_offsets), _t(edge_i), _t(edge_j), _t(edge_kind), _t(edge_z), _t(edge_w),
+                                    _t(node_fixed), _t(poses_out), _t(cost_initial), _t(cost_final), _t(iters),
+                                    _t(status)), "pg_solve")
+
+    def pg_edges_from_transforms(self, T, z):
+        """Device tensors: T [E, 3, 4] float32 ([R | t], what pose_from_matches gives) -> z [E, 7]
+        float32 edge measurements, by poses_to_q7's arithmetic on the device."""
+        check(lib().mv_pg_edges_from_transforms_dev(self.h, T.shape[0], _t(T), _t(z)), "pg_edges_from_transforms")
 
     # ---------------- loop closure (include/loop_closure.h) ----------------
     def bow_words(self, voc, desc_scales, desc, num_sel, patches, base, wid, word_id, best_match, scores=None):
