@@ -14,7 +14,8 @@
  *   edges may join one pair; edge_kind MV_PG_EDGE_SE3 or MV_PG_EDGE_DIRECTION; edge_z [7] fp32 the
  *   measured T_j . T_i^-1 in trajectory.h's convention (it maps frame i to frame j) -- for a
  *   direction edge its translation is a unit vector, used as given and not renormalised (a monocular
- *   pair pose has no scale); edge_w [2] fp32 = (w_rot, w_trans), both >= 0 and finite.
+ *   pair pose has no scale; a frame localised against the map by absolute_pose.h has one, and its
+ *   pose gives a full SE3 edge); edge_w [2] fp32 = (w_rot, w_trans), both >= 0 and finite.
  *
  * State.  Always fp32.  All solver arithmetic is float64, inputs promoted once; a candidate state
  *   is the double update rounded once to fp32, and every cost is evaluated at a rounded state.  Only

@@ -45,6 +45,7 @@
 #include <algorithm>
 
 #include "mv_internal.hpp"
+#include "mv_quat.hpp"
 #include "pose_graph.h"
 
 namespace {
@@ -635,24 +636,9 @@ __global__ void k_pg_edges_from_transforms(int E, const float *__restrict__ T, f
         for (int c = 0; c < 3; c++) R[r][c] = T[12l * k + 4 * r + c];
         t[r] = T[12l * k + 4 * r + 3];
     }
-    const double d[4] = {((1.0 + R[0][0]) + R[1][1]) + R[2][2], ((1.0 + R[0][0]) - R[1][1]) - R[2][2],
-                         ((1.0 - R[0][0]) + R[1][1]) - R[2][2], ((1.0 - R[0][0]) - R[1][1]) + R[2][2]};
-    int c = 0;
-    for (int i = 1; i < 4; i++)
-        if (d[i] > d[c]) c = i;  // the first largest
-    const double s = 2.0 * sqrt(d[c]);
     double q[4];
-    if (c == 0)
-        q[0] = 0.25 * s, q[1] = (R[2][1] - R[1][2]) / s, q[2] = (R[0][2] - R[2][0]) / s, q[3] = (R[1][0] - R[0][1]) / s;
-    else if (c == 1)
-        q[0] = (R[2][1] - R[1][2]) / s, q[1] = 0.25 * s, q[2] = (R[0][1] + R[1][0]) / s, q[3] = (R[0][2] + R[2][0]) / s;
-    else if (c == 2)
-        q[0] = (R[0][2] - R[2][0]) / s, q[1] = (R[0][1] + R[1][0]) / s, q[2] = 0.25 * s, q[3] = (R[1][2] + R[2][1]) / s;
-    else
-        q[0] = (R[1][0] - R[0][1]) / s, q[1] = (R[0][2] + R[2][0]) / s, q[2] = (R[1][2] + R[2][1]) / s, q[3] = 0.25 * s;
-    const double nn = sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
-    const double sign = q[0] / nn < 0.0 ? -1.0 : 1.0;
-    for (int i = 0; i < 4; i++) z[7l * k + i] = (float)(sign * (q[i] / nn));
+    mv::rot_to_quat(R, q);
+    for (int i = 0; i < 4; i++) z[7l * k + i] = (float)q[i];
     for (int i = 0; i < 3; i++) z[7l * k + 4 + i] = (float)t[i];
 }
 

@@ -86,7 +86,16 @@ class PgParams(ctypes.Structure):
                 ("lambda_max", _D), ("diag_floor", _D), ("rel_tol", _D), ("huber", _D)]
 
 
+class PnpParams(ctypes.Structure):
+    """mv_pnp_params (include/absolute_pose.h)."""
+    _fields_ = [("hypotheses", _I), ("refine_rounds", _I), ("min_inliers", _I), ("max_iters", _I),
+                ("seed", ctypes.c_ulonglong), ("inlier_thresh_px", _D), ("min_depth", _D), ("lambda_init", _D),
+                ("lambda_up", _D), ("lambda_down", _D), ("lambda_min", _D), ("lambda_max", _D), ("diag_floor", _D),
+                ("rel_tol", _D), ("huber_px", _D)]
+
+
 BA_MAX_POSES = 16  # MV_BA_MAX_POSES
+PNP_MAX_CAP = 1024  # MV_PNP_MAX_CAP
 PG_MAX_NODES = 512  # MV_PG_MAX_NODES
 PG_EDGE_SE3, PG_EDGE_DIRECTION = 0, 1
 LDMK_LOW_PARALLAX, LDMK_BEHIND, LDMK_REPROJ, LDMK_DEGENERATE = 1, 2, 4, 8
@@ -218,6 +227,9 @@ def lib():
             "mv_pg_solve_dev": (_I, [_P, _P, _I, _I, _I, _I] + [_P] * 13),
             "mv_pg_envelope_host": (_I, [_I, _I, _P, _P, _P]),
             "mv_pg_edges_from_transforms_dev": (_I, [_P, _I, _P, _P]),
+            "mv_pnp_params_default": (None, [_P]),
+            "mv_pnp_correspondences_dev": (_I, [_P, _I, _I, _I, _P, ctypes.c_long] + [_P] * 9),
+            "mv_pnp_solve_dev": (_I, [_P, _P, _I, _I] + [_P] * 11),
         }
         for name, (res, args) in sig.items():
             try:
@@ -474,6 +486,16 @@ def pg_params(**kw):
     return p
 
 
+def pnp_params(**kw):
+    """mv_pnp_params with its defaults (hypotheses 256, refine_rounds 2, min_inliers 6, max_iters 10,
+    inlier_thresh_px 2, min_depth 0.1 and mv_ba_params' LM fields)."""
+    p = PnpParams()
+    lib().mv_pnp_params_default(ctypes.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
 def pg_envelope(nodes, edge_i, edge_j, node_fixed=None):
     """The row envelope of one pose graph in 6 x 6 blocks (mv_pg_envelope_host), to size pg_solve's
     env_cap: edge_i / edge_j with local node ids in [0, nodes), node_fixed [nodes] (None: node 0 is
@@ -494,7 +516,8 @@ def poses_to_q7(poses12):
     include/factors.h and Context.tracks_triangulate.  Host, numpy only (not on the hot path).
     A monocular chain is built from per-pair translations of unit length, so its translations
     carry no metric scale: the caller supplies the scale (multiply each pair's t before chaining,
-    or the chained t here) -- landmarks triangulated from the poses inherit it."""
+    or the chained t here) -- landmarks triangulated from the poses inherit it, and Context.pnp_solve
+    (include/absolute_pose.h) carries it on to a new frame."""
     P = np.asarray(poses12, np.float64).reshape(-1, 3, 4)
     out = np.zeros((P.shape[0], 7), np.float64)
     for k in range(P.shape[0]):
@@ -886,6 +909,34 @@ class Context:
         """Device tensors: T [E, 3, 4] float32 ([R | t], what pose_from_matches gives) -> z [E, 7]
         float32 edge measurements, by poses_to_q7's arithmetic on the device."""
         check(lib().mv_pg_edges_from_transforms_dev(self.h, T.shape[0], _t(T), _t(z)), "pg_edges_from_transforms")
+
+    # ---------------- map localisation (include/absolute_pose.h) ----------------
+    pnp_params = staticmethod(pnp_params)
+
+    def pnp_correspondences(self, track_id, ldmk_flags, landmarks, match_idx, n_prev, n_new, kp_new, pts3, pts2,
+                            count):
+        """Device tensors: track_id [B, cap] int32, the last map frame's row of tracks_link's track_id
+        (a view such as track_id[:, F - 1] goes in in place: rows contiguous, any stride between
+        problems), ldmk_flags [B, track_cap], landmarks [B, track_cap, 3], match_idx [B, cap] (last map
+        frame -> new frame), n_prev / n_new [B], kp_new [B, cap, 2] -> pts3 [B, cap, 3], pts2
+        [B, cap, 2] float32, count [B] int32: the 3D-2D pairs of pnp_solve."""
+        B, cap = match_idx.shape
+        assert track_id.shape == (B, cap) and (cap == 1 or track_id.stride(1) == 1)
+        check(lib().mv_pnp_correspondences_dev(self.h, B, cap, ldmk_flags.shape[1], _t(track_id),
+                                               track_id.stride(0) if B > 1 else cap, _t(ldmk_flags), _t(landmarks),
+                                               _t(match_idx), _t(n_prev), _t(n_new), _t(kp_new), _t(pts3), _t(pts2),
+                                               _t(count)), "pnp_correspondences")
+
+    def pnp_solve(self, n, pts3, pts2, cameras, pose_out, inlier, num_inliers, best_hyp, status, cost,
+                  pose_prior=None, params=None):
+        """Device tensors: n [B] int32, pts3 [B, cap, 3], pts2 [B, cap, 2], cameras [B, 4] float32,
+        pose_prior [B, 7] float32 or None -> pose_out [B, 7] float32 (camera-from-world, the map's
+        scale), inlier [B, cap], num_inliers / best_hyp / status [B] int32, cost [B] float64."""
+        B, cap = pts3.shape[0], pts3.shape[1]
+        p = params or pnp_params()
+        check(lib().mv_pnp_solve_dev(self.h, ctypes.byref(p), B, cap, _t(n), _t(pts3), _t(pts2), _t(cameras),
+                                     _t(pose_prior), _t(pose_out), _t(inlier), _t(num_inliers), _t(best_hyp),
+                                     _t(status), _t(cost)), "pnp_solve")
 
     # ---------------- loop closure (include/loop_closure.h) ----------------
     def bow_words(self, voc, desc_scales, desc, num_sel, patches, base, wid, word_id, best_match, scores=None):
