@@ -94,6 +94,11 @@ class PnpParams(ctypes.Structure):
                 ("rel_tol", _D), ("huber_px", _D)]
 
 
+class MapParams(ctypes.Structure):
+    """mv_map_params (include/map_match.h)."""
+    _fields_ = [("radius_px", _D), ("min_depth", _D), ("thresh", _D), ("ratio", _D), ("width", _I), ("height", _I)]
+
+
 BA_MAX_POSES = 16  # MV_BA_MAX_POSES
 PNP_MAX_CAP = 1024  # MV_PNP_MAX_CAP
 PG_MAX_NODES = 512  # MV_PG_MAX_NODES
@@ -230,6 +235,9 @@ def lib():
             "mv_pnp_params_default": (None, [_P]),
             "mv_pnp_correspondences_dev": (_I, [_P, _I, _I, _I, _P, ctypes.c_long] + [_P] * 9),
             "mv_pnp_solve_dev": (_I, [_P, _P, _I, _I] + [_P] * 11),
+            "mv_map_params_default": (None, [_P]),
+            "mv_map_descriptors_dev": (_I, [_P, _I, _I, _I, _I] + [_P] * 5),
+            "mv_map_match_dev": (_I, [_P, _P, _I, _I, _I] + [_P] * 17),
         }
         for name, (res, args) in sig.items():
             try:
@@ -491,6 +499,16 @@ def pnp_params(**kw):
     inlier_thresh_px 2, min_depth 0.1 and mv_ba_params' LM fields)."""
     p = PnpParams()
     lib().mv_pnp_params_default(ctypes.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def map_params(**kw):
+    """mv_map_params with its defaults (radius_px 16, min_depth 0.1, thresh 0.8, ratio 0 = off, and
+    the width / height binning hint)."""
+    p = MapParams()
+    lib().mv_map_params_default(ctypes.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     return p
@@ -937,6 +955,33 @@ class Context:
         check(lib().mv_pnp_solve_dev(self.h, ctypes.byref(p), B, cap, _t(n), _t(pts3), _t(pts2), _t(cameras),
                                      _t(pose_prior), _t(pose_out), _t(inlier), _t(num_inliers), _t(best_hyp),
                                      _t(status), _t(cost)), "pnp_solve")
+
+    # ---------------- map matching by projection (include/map_match.h) ----------------
+    map_params = staticmethod(map_params)
+
+    def map_descriptors(self, track_id, ldmk_flags, desc, ldmk_obs, ldmk_desc):
+        """Device tensors: track_id [B, F, cap] int32 (tracks_link), ldmk_flags [B, track_cap] int32,
+        desc [B, F, cap, 256] float32 -> ldmk_obs [B, track_cap] int32 (f * cap + i of the usable track's
+        last observation, -1 otherwise), ldmk_desc [B, track_cap, 256] float32 (that row, or zeros)."""
+        B, F, cap = track_id.shape
+        assert desc.shape == (B, F, cap, 256) and ldmk_desc.shape == (B, ldmk_flags.shape[1], 256)
+        check(lib().mv_map_descriptors_dev(self.h, B, F, cap, ldmk_flags.shape[1], _t(track_id), _t(ldmk_flags),
+                                           _t(desc), _t(ldmk_obs), _t(ldmk_desc)), "map_descriptors")
+
+    def map_match(self, n_ldmk, landmarks, ldmk_flags, ldmk_desc, pose_prior, cameras, n_new, kp_new, desc_new,
+                  proj, ncand, match_idx, match_score, pts3, pts2, pair_ldmk, count, params=None):
+        """Device tensors: n_ldmk [B] int32, landmarks [B, L, 3], ldmk_flags [B, L] int32, ldmk_desc
+        [B, L, 256], pose_prior [B, 7], cameras [B, 4], n_new [B] int32, kp_new [B, cap, 2], desc_new
+        [B, cap, 256] -> proj [B, L, 2] float32, ncand / match_idx [B, L] int32, match_score [B, L] float32,
+        and the pairs in pnp_solve's layout: pts3 [B, cap, 3], pts2 [B, cap, 2], pair_ldmk [B, cap], count [B]."""
+        B, L = ldmk_flags.shape
+        cap = kp_new.shape[1]
+        assert ldmk_desc.shape == (B, L, 256) and desc_new.shape == (B, cap, 256) and landmarks.shape == (B, L, 3)
+        p = params or map_params()
+        check(lib().mv_map_match_dev(self.h, ctypes.byref(p), B, L, cap, _t(n_ldmk), _t(landmarks), _t(ldmk_flags),
+                                     _t(ldmk_desc), _t(pose_prior), _t(cameras), _t(n_new), _t(kp_new), _t(desc_new),
+                                     _t(proj), _t(ncand), _t(match_idx), _t(match_score), _t(pts3), _t(pts2),
+                                     _t(pair_ldmk), _t(count)), "map_match")
 
     # ---------------- loop closure (include/loop_closure.h) ----------------
     def bow_words(self, voc, desc_scales, desc, num_sel, patches, base, wid, word_id, best_match, scores=None):
