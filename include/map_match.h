@@ -61,8 +61,9 @@
  * per-problem state of the present kernels fits LDS and the outputs themselves, so they take none).
  *
  * Out of scope: viewing-angle and scale gates, medoid descriptors (the last observation's row
- * stands for the landmark), appending the found observations to the tracks, whole-map search at
- * workload sizes (mv_match_allpairs_f32_dev does that), choosing the prior.
+ * stands for the landmark), whole-map search at workload sizes (mv_match_allpairs_f32_dev does
+ * that), choosing the prior.  Appending the found observations to the tracks is mv_map_extend_dev
+ * (map_update.h): it takes pair_ldmk, count and match_idx as they are written here.
  */
 #ifndef MV_MAP_MATCH_H
 #define MV_MAP_MATCH_H

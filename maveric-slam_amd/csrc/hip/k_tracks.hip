@@ -18,7 +18,8 @@
 // Triangulate: k_tr_triangulate, a thread per track; two walks along match_idx (normal equations,
 //   then depth / reprojection checks), all arithmetic float64 in the order of
 //   tests/tracks_reference.py (no contraction: -ffp-contract=off), the next observation's index,
-//   keypoint, pose and camera loaded before the current one's arithmetic.
+//   keypoint, pose and camera loaded before the current one's arithmetic.  The arithmetic lives in
+//   tr_midpoint.hpp and the claim's key in tr_claim.hpp, both shared with k_mapupd.hip.
 // Factors: k_tr_fcount (ballot count per 256-node block, flat over the batch), k_tr_scan (one
 //   workgroup over the block counts; total, status), k_tr_femit (ballot prefix -> slot; the
 //   first node of every frame writes pose_offsets).
@@ -26,19 +27,15 @@
 
 #include "feature_tracks.h"
 #include "mv_internal.hpp"
+#include "tr_claim.hpp"
+#include "tr_midpoint.hpp"
 
 namespace {
 
 constexpr int NB = 256;  // nodes per workgroup of the per-node kernels
 
-__device__ __forceinline__ int clampn(int v, int cap) { return v < 0 ? 0 : (v > cap ? cap : v); }
-
-// fp32 -> u32 with the order of `<` on non-NaN values (-0 == +0)
-__device__ __forceinline__ unsigned ordered_bits(float f) {
-    if (f == 0.f) f = 0.f;
-    const unsigned u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
+using tr::block_rank;
+using tr::clampn;
 
 __global__ __launch_bounds__(256) void k_tr_claim(int F, int cap, const int *__restrict__ n,
                                                   const int *__restrict__ midx, const float *__restrict__ mscore,
@@ -53,13 +50,7 @@ __global__ __launch_bounds__(256) void k_tr_claim(int F, int cap, const int *__r
     for (int i = tid; i < n0; i += 256) {
         const int j = midx[pair + i];
         if (j < 0 || j >= n1) continue;
-        unsigned hi = 1u;
-        if (mscore) {
-            const float sc = mscore[pair + i];
-            if (sc != sc) continue;
-            hi = ordered_bits(sc);
-        }
-        atomicMax(&s_key[j], ((unsigned long long)hi << 32) | (unsigned)~i);
+        tr::claim_propose(s_key, i, j, mscore ? mscore + pair : nullptr);
     }
     __syncthreads();
     for (int i = tid; i < cap; i += 256) {
@@ -68,7 +59,7 @@ __global__ __launch_bounds__(256) void k_tr_claim(int F, int cap, const int *__r
             const int j = midx[pair + i];
             // the low word names the winner (never 0: i >= 0); a row that made no proposal (NaN
             // score) is never named
-            if (j >= 0 && j < n1 && (unsigned)s_key[j] == (unsigned)~i) a = j;
+            if (j >= 0 && j < n1 && tr::claim_won(s_key[j], i)) a = j;
         }
         acc[node0 + i] = a;
         hasprev[node1 + i] = s_key[i] != 0ull ? 1 : 0;
@@ -151,17 +142,6 @@ __global__ __launch_bounds__(256) void k_tr_scan(int nb, int mode, int limit, in
     }
 }
 
-// rank of this thread among the threads of the block with `flag` (NB = 256: 4 waves)
-__device__ __forceinline__ int block_rank(bool flag, int *s_wave) {
-    const unsigned long long m = __ballot(flag);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) s_wave[wave] = __popcll(m);
-    __syncthreads();
-    int r = __popcll(m & ((1ull << lane) - 1ull));
-    for (int w = 0; w < wave; w++) r += s_wave[w];
-    return r;
-}
-
 __global__ __launch_bounds__(NB) void k_tr_number(int F, int cap, int nb, int track_cap, const int *__restrict__ acc,
                                                   const int *__restrict__ rootlen, const int *__restrict__ blockoff,
                                                   const int *__restrict__ status, int *__restrict__ track_id,
@@ -184,36 +164,10 @@ __global__ __launch_bounds__(NB) void k_tr_number(int F, int cap, int nb, int tr
 }
 
 // ---------------------------------------------------------------------------------------------
-// Triangulation.  Every line below follows tests/tracks_reference.py operation for operation.
+// Triangulation.  tr_midpoint.hpp follows tests/tracks_reference.py operation for operation.
 // ---------------------------------------------------------------------------------------------
-struct Obs {
-    double q[7], k[4], u, v;
-};
-
-__device__ __forceinline__ void load_obs(Obs &o, const float *__restrict__ pose, const float *__restrict__ cam,
-                                         const float *__restrict__ kp, size_t frame, size_t node) {
-#pragma unroll
-    for (int c = 0; c < 7; c++) o.q[c] = (double)pose[7 * frame + c];
-#pragma unroll
-    for (int c = 0; c < 4; c++) o.k[c] = (double)cam[4 * frame + c];
-    const float2 p = *reinterpret_cast<const float2 *>(kp + 2 * node);
-    o.u = (double)p.x;
-    o.v = (double)p.y;
-}
-
-__device__ __forceinline__ void rot(const double *q, double *R) {
-    const double w = q[0], x = q[1], y = q[2], z = q[3];
-    const double ww = w * w, xx = x * x, yy = y * y, zz = z * z;
-    R[0] = ((ww + xx) - yy) - zz;
-    R[1] = 2.0 * (x * y - w * z);
-    R[2] = 2.0 * (x * z + w * y);
-    R[3] = 2.0 * (x * y + w * z);
-    R[4] = ((ww - xx) + yy) - zz;
-    R[5] = 2.0 * (y * z - w * x);
-    R[6] = 2.0 * (x * z - w * y);
-    R[7] = 2.0 * (y * z + w * x);
-    R[8] = ((ww - xx) - yy) + zz;
-}
+using tr::load_obs;
+using tr::Obs;
 
 __global__ __launch_bounds__(64) void k_tr_triangulate(int B, int F, int cap, int track_cap, double cos_min,
                                                        double min_depth, double max_reproj,
@@ -236,17 +190,12 @@ __global__ __launch_bounds__(64) void k_tr_triangulate(int B, int F, int cap, in
     const int f0 = first / cap, i0 = first - f0 * cap;
     len = min(len, F - f0);
     if (len <= 0) {  // an unused entry
-        ldmk[3 * gt] = 0.f;
-        ldmk[3 * gt + 1] = 0.f;
-        ldmk[3 * gt + 2] = 0.f;
-        flags_out[gt] = MV_LDMK_DEGENERATE;
+        tr::store_landmark(ldmk, flags_out, gt, 0.f, 0.f, 0.f, MV_LDMK_DEGENERATE);
         return;
     }
     const size_t fbase = (size_t)s * F, nbase = (size_t)s * N, pbase = (size_t)s * (F - 1) * cap;
 
-    double A00 = 0.0, A01 = 0.0, A02 = 0.0, A11 = 0.0, A12 = 0.0, A22 = 0.0, b0 = 0.0, b1 = 0.0, b2 = 0.0;
-    double c00 = 0.0, c01 = 0.0, c02 = 0.0, e00 = 0.0, e01 = 0.0, e02 = 0.0;
-    double mindot = INFINITY;
+    tr::Midpoint mp;
     int count = 0;
     {
         Obs cur, nxt;
@@ -261,58 +210,16 @@ __global__ __launch_bounds__(64) void k_tr_triangulate(int B, int F, int cap, in
                 if (inext < 0 || inext >= cap) inext = -1;
             }
             if (inext >= 0) load_obs(nxt, poses, cams, kp, fbase + f + 1, nbase + (size_t)(f + 1) * cap + inext);
-            double R[9];
-            rot(cur.q, R);
-            const double r0 = (cur.u - cur.k[2]) / cur.k[0], r1 = (cur.v - cur.k[3]) / cur.k[1];
-            const double e0 = (R[0] * r0 + R[3] * r1) + R[6];
-            const double e1 = (R[1] * r0 + R[4] * r1) + R[7];
-            const double e2 = (R[2] * r0 + R[5] * r1) + R[8];
-            const double nrm = sqrt((e0 * e0 + e1 * e1) + e2 * e2);
-            const double d0 = e0 / nrm, d1 = e1 / nrm, d2 = e2 / nrm;
-            const double tx = cur.q[4], ty = cur.q[5], tz = cur.q[6];
-            const double c0 = -((R[0] * tx + R[3] * ty) + R[6] * tz);
-            const double c1 = -((R[1] * tx + R[4] * ty) + R[7] * tz);
-            const double c2 = -((R[2] * tx + R[5] * ty) + R[8] * tz);
-            if (k == 0) {
-                c00 = c0, c01 = c1, c02 = c2;
-                e00 = d0, e01 = d1, e02 = d2;
-            } else {
-                const double dot = (e00 * d0 + e01 * d1) + e02 * d2;
-                if (dot < mindot) mindot = dot;
-            }
-            const double m00 = 1.0 - d0 * d0, m11 = 1.0 - d1 * d1, m22 = 1.0 - d2 * d2;
-            const double m01 = -(d0 * d1), m02 = -(d0 * d2), m12 = -(d1 * d2);
-            A00 = A00 + m00;
-            A01 = A01 + m01;
-            A02 = A02 + m02;
-            A11 = A11 + m11;
-            A12 = A12 + m12;
-            A22 = A22 + m22;
-            const double g0 = c0 - c00, g1 = c1 - c01, g2 = c2 - c02;
-            b0 = b0 + ((m00 * g0 + m01 * g1) + m02 * g2);
-            b1 = b1 + ((m01 * g0 + m11 * g1) + m12 * g2);
-            b2 = b2 + ((m02 * g0 + m12 * g1) + m22 * g2);
+            mp.add(cur, k == 0);
             count++;
             if (inext < 0) break;
             cur = nxt;
             i = inext;
         }
     }
-    int flags = 0;
-    if (mindot > cos_min) flags |= MV_LDMK_LOW_PARALLAX;
-    const double C00 = A11 * A22 - A12 * A12, C01 = A02 * A12 - A01 * A22, C02 = A01 * A12 - A02 * A11;
-    const double C11 = A00 * A22 - A02 * A02, C12 = A01 * A02 - A00 * A12, C22 = A00 * A11 - A01 * A01;
-    const double det = (A00 * C00 + A01 * C01) + A02 * C02;
-    const double X0 = c00 + ((C00 * b0 + C01 * b1) + C02 * b2) / det;
-    const double X1 = c01 + ((C01 * b0 + C11 * b1) + C12 * b2) / det;
-    const double X2 = c02 + ((C02 * b0 + C12 * b1) + C22 * b2) / det;
-    const bool finite = isfinite(X0) && isfinite(X1) && isfinite(X2);
-    if (!(det > 0.0) || !finite) {
-        flags |= MV_LDMK_DEGENERATE;
-        ldmk[3 * gt] = 0.f;
-        ldmk[3 * gt + 1] = 0.f;
-        ldmk[3 * gt + 2] = 0.f;
-        flags_out[gt] = flags;
+    int flags = mp.solve(cos_min);
+    if (flags & MV_LDMK_DEGENERATE) {
+        tr::store_landmark(ldmk, flags_out, gt, 0.f, 0.f, 0.f, flags);
         return;
     }
     const double mr2 = max_reproj * max_reproj;
@@ -325,24 +232,13 @@ __global__ __launch_bounds__(64) void k_tr_triangulate(int B, int F, int cap, in
             inext = -1;
             if (k + 1 < count) inext = midx[pbase + (size_t)f * cap + i];  // in range: walked above
             if (inext >= 0) load_obs(nxt, poses, cams, kp, fbase + f + 1, nbase + (size_t)(f + 1) * cap + inext);
-            double R[9];
-            rot(cur.q, R);
-            const double p0 = ((R[0] * X0 + R[1] * X1) + R[2] * X2) + cur.q[4];
-            const double p1 = ((R[3] * X0 + R[4] * X1) + R[5] * X2) + cur.q[5];
-            const double p2 = ((R[6] * X0 + R[7] * X1) + R[8] * X2) + cur.q[6];
-            if (p2 < min_depth) flags |= MV_LDMK_BEHIND;
-            const double du = (cur.k[0] * (p0 / p2) + cur.k[2]) - cur.u;
-            const double dv = (cur.k[1] * (p1 / p2) + cur.k[3]) - cur.v;
-            if (du * du + dv * dv > mr2) flags |= MV_LDMK_REPROJ;
+            flags |= mp.check(cur, min_depth, mr2);
             if (inext < 0) break;
             cur = nxt;
             i = inext;
         }
     }
-    ldmk[3 * gt] = (float)X0;
-    ldmk[3 * gt + 1] = (float)X1;
-    ldmk[3 * gt + 2] = (float)X2;
-    flags_out[gt] = flags;
+    tr::store_landmark(ldmk, flags_out, gt, (float)mp.X0, (float)mp.X1, (float)mp.X2, flags);
 }
 
 // ---------------------------------------------------------------------------------------------

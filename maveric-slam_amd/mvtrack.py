@@ -238,6 +238,9 @@ def lib():
             "mv_map_params_default": (None, [_P]),
             "mv_map_descriptors_dev": (_I, [_P, _I, _I, _I, _I] + [_P] * 5),
             "mv_map_match_dev": (_I, [_P, _P, _I, _I, _I] + [_P] * 17),
+            "mv_map_index_dev": (_I, [_P, _I, _I, _I, _I, _I] + [_P] * 7),
+            "mv_map_extend_dev": (_I, [_P, _I, _I, _I, _I, _I] + [_P] * 19),
+            "mv_map_triangulate_dev": (_I, [_P, _P, _I, _I, _I, _I, _I] + [_P] * 11),
         }
         for name, (res, args) in sig.items():
             try:
@@ -982,6 +985,49 @@ class Context:
                                      _t(ldmk_desc), _t(pose_prior), _t(cameras), _t(n_new), _t(kp_new), _t(desc_new),
                                      _t(proj), _t(ncand), _t(match_idx), _t(match_score), _t(pts3), _t(pts2),
                                      _t(pair_ldmk), _t(count)), "map_match")
+
+    # ---------------- map update (include/map_update.h) ----------------
+    def map_index(self, track_id, num_tracks, status, track_first, track_len, next_obs, track_last, f_count=None):
+        """Device tensors: track_id [B, F, cap], num_tracks / status [B] (tracks_link; rows of frames not
+        yet used hold -1) -> track_first / track_len / track_last [B, track_cap], next_obs [B, F, cap]:
+        the observation chains of the frames below f_count (None: all F)."""
+        B, F, cap = track_id.shape
+        assert next_obs.shape == (B, F, cap) and track_last.shape == track_first.shape == track_len.shape
+        check(lib().mv_map_index_dev(self.h, B, F, cap, track_first.shape[1], F if f_count is None else int(f_count),
+                                     _t(track_id), _t(num_tracks), _t(status), _t(track_first), _t(track_len),
+                                     _t(next_obs), _t(track_last)), "map_index")
+
+    def map_extend(self, f_new, n_prev, n_new, match_idx, match_score, status, track_id, num_tracks, track_first,
+                   track_len, next_obs, track_last, touched, n_extended, n_created, ext_status, pair_ldmk=None,
+                   pair_count=None, map_idx=None, inlier=None):
+        """Appends frame f_new to the map state (track_id [B, F, cap], num_tracks [B], track_first /
+        track_len / track_last [B, track_cap], next_obs [B, F, cap], all updated in place).  Device
+        tensors: n_prev / n_new [B], match_idx / match_score [B, cap] from frame f_new - 1 to f_new
+        (match_score may be None), status [B]; optionally map_match's pair_ldmk [B, cap], pair_count [B]
+        and match_idx [B, track_cap] (map_idx) with pnp_solve's inlier [B, cap] -- all four or none ->
+        touched [B, track_cap], n_extended / n_created / ext_status [B] int32."""
+        B, F, cap = track_id.shape
+        assert match_idx.shape == (B, cap) and next_obs.shape == (B, F, cap)
+        assert touched.shape == track_last.shape == track_first.shape == track_len.shape
+        check(lib().mv_map_extend_dev(self.h, B, F, cap, track_first.shape[1], int(f_new), _t(n_prev), _t(n_new),
+                                      _t(match_idx), _t(match_score), _t(pair_ldmk), _t(pair_count), _t(map_idx),
+                                      _t(inlier), _t(status), _t(track_id), _t(num_tracks), _t(track_first),
+                                      _t(track_len), _t(next_obs), _t(track_last), _t(touched), _t(n_extended),
+                                      _t(n_created), _t(ext_status)), "map_extend")
+
+    def map_triangulate(self, poses, cameras, kp, num_tracks, track_first, track_len, next_obs, status, landmarks,
+                        ldmk_flags, f_count=None, select=None, params=None):
+        """Device tensors: poses [B, F, 7], cameras [B, F, 4], kp [B, F, cap, 2] and the map state ->
+        landmarks [B, track_cap, 3] float32, ldmk_flags [B, track_cap] int32 from the observation chains
+        of the frames below f_count (None: all F).  select [B, track_cap] int32 (map_extend's touched):
+        only the entries with a nonzero select are recomputed; None: all."""
+        B, F, cap = next_obs.shape
+        assert kp.shape == (B, F, cap, 2) and (select is None or select.shape == ldmk_flags.shape)
+        p = params or landmark_params()
+        check(lib().mv_map_triangulate_dev(self.h, ctypes.byref(p), B, F, cap, track_first.shape[1],
+                                           F if f_count is None else int(f_count), _t(poses), _t(cameras), _t(kp),
+                                           _t(num_tracks), _t(track_first), _t(track_len), _t(next_obs), _t(status),
+                                           _t(select), _t(landmarks), _t(ldmk_flags)), "map_triangulate")
 
     # ---------------- loop closure (include/loop_closure.h) ----------------
     def bow_words(self, voc, desc_scales, desc, num_sel, patches, base, wid, word_id, best_match, scores=None):
