@@ -57,9 +57,10 @@
  * before capturing in a graph) and scale with the launch's workgroup count, not with batch.
  * Limits: 1 <= frames <= MV_BA_MAX_POSES, batch * frames and batch * track_cap < 2^31.
  *
- * Out of scope: sliding a window along a sequence, marginalisation and priors; re-numbering
- * landmarks; anything feeding mv_lba_schur_dev.  Triangulating and flagging landmarks again from
- * all their observations is mv_map_triangulate_dev (map_update.h), not part of the solve.
+ * Out of scope: marginalisation and priors; re-numbering landmarks; anything feeding
+ * mv_lba_schur_dev.  Choosing a window of a sequence longer than MV_BA_MAX_POSES frames, gathering it
+ * into this layout and writing its poses back is ba_window.h, not part of the solve; triangulating and
+ * flagging landmarks again from all their observations is mv_map_triangulate_dev (map_update.h).
  */
 #ifndef MV_BUNDLE_ADJUST_H
 #define MV_BUNDLE_ADJUST_H

@@ -22,13 +22,15 @@
 //   tr_midpoint.hpp and the claim's key in tr_claim.hpp, both shared with k_mapupd.hip.
 // Factors: k_tr_fcount (ballot count per 256-node block, flat over the batch), k_tr_scan (one
 //   workgroup over the block counts; total, status), k_tr_femit (ballot prefix -> slot; the
-//   first node of every frame writes pose_offsets).
+//   first node of every frame writes pose_offsets).  The scan itself is tr_scan.hpp, shared with
+//   k_bawin.hip's factor pass over a window.
 #include <math.h>
 
 #include "feature_tracks.h"
 #include "mv_internal.hpp"
 #include "tr_claim.hpp"
 #include "tr_midpoint.hpp"
+#include "tr_scan.hpp"
 
 namespace {
 
@@ -110,25 +112,7 @@ __global__ __launch_bounds__(256) void k_tr_scan(int nb, int mode, int limit, in
                                                  int *__restrict__ track_first, int *__restrict__ track_len) {
     __shared__ int s_part[256];
     const int seg = blockIdx.x, tid = threadIdx.x;
-    int *v = sums + (size_t)seg * nb;
-    const int per = (nb + 255) / 256, lo = min(tid * per, nb), hi = min(lo + per, nb);
-    int sum = 0;
-    for (int k = lo; k < hi; k++) sum += v[k];
-    s_part[tid] = sum;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {  // inclusive Hillis-Steele scan of the 256 partials
-        const int add = tid >= off ? s_part[tid - off] : 0;
-        __syncthreads();
-        s_part[tid] += add;
-        __syncthreads();
-    }
-    int run = s_part[tid] - sum;
-    const int total = s_part[255];
-    for (int k = lo; k < hi; k++) {
-        const int c = v[k];
-        v[k] = run;
-        run += c;
-    }
+    const int total = tr::scan_exclusive_256(nb, sums + (size_t)seg * nb, s_part);
     const bool over = total > limit;
     if (tid == 0) {
         total_out[seg] = total;

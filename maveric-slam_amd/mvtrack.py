@@ -94,6 +94,11 @@ class PnpParams(ctypes.Structure):
                 ("rel_tol", _D), ("huber_px", _D)]
 
 
+class BaWindowParams(ctypes.Structure):
+    """mv_ba_window_params (include/ba_window.h)."""
+    _fields_ = [("min_shared", _I), ("n_fixed", _I), ("min_obs", _I)]
+
+
 class MapParams(ctypes.Structure):
     """mv_map_params (include/map_match.h)."""
     _fields_ = [("radius_px", _D), ("min_depth", _D), ("thresh", _D), ("ratio", _D), ("width", _I), ("height", _I)]
@@ -241,6 +246,11 @@ def lib():
             "mv_map_index_dev": (_I, [_P, _I, _I, _I, _I, _I] + [_P] * 7),
             "mv_map_extend_dev": (_I, [_P, _I, _I, _I, _I, _I] + [_P] * 19),
             "mv_map_triangulate_dev": (_I, [_P, _P, _I, _I, _I, _I, _I] + [_P] * 11),
+            "mv_ba_window_params_default": (None, [_P]),
+            "mv_map_covisibility_dev": (_I, [_P, _I, _I, _I, _I, _I] + [_P] * 6),
+            "mv_ba_window_select_dev": (_I, [_P, _P, _I, _I, _I, _I] + [_P] * 7),
+            "mv_ba_window_factors_dev": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I] + [_P] * 15),
+            "mv_ba_window_scatter_dev": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
         }
         for name, (res, args) in sig.items():
             try:
@@ -512,6 +522,15 @@ def map_params(**kw):
     the width / height binning hint)."""
     p = MapParams()
     lib().mv_map_params_default(ctypes.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def ba_window_params(**kw):
+    """mv_ba_window_params with its defaults (min_shared 15, n_fixed 2, min_obs 2)."""
+    p = BaWindowParams()
+    lib().mv_ba_window_params_default(ctypes.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     return p
@@ -1028,6 +1047,59 @@ class Context:
                                            F if f_count is None else int(f_count), _t(poses), _t(cameras), _t(kp),
                                            _t(num_tracks), _t(track_first), _t(track_len), _t(next_obs), _t(status),
                                            _t(select), _t(landmarks), _t(ldmk_flags)), "map_triangulate")
+
+    # ---------------- local BA windows (include/ba_window.h) ----------------
+    ba_window_params = staticmethod(ba_window_params)
+
+    def map_covisibility(self, track_id, num_tracks, status, ldmk_flags, f_q, covis, f_count=None):
+        """Device tensors: the map state track_id [B, F, cap], num_tracks / status [B], ldmk_flags
+        [B, track_cap] and the query frames f_q [B] int32 -> covis [B, F] int32: the usable landmarks
+        every frame below f_count (None: all F) shares with frame f_q."""
+        B, F, cap = track_id.shape
+        assert covis.shape == (B, F) and f_q.shape == (B,)
+        check(lib().mv_map_covisibility_dev(self.h, B, F, cap, ldmk_flags.shape[1],
+                                            F if f_count is None else int(f_count), _t(track_id), _t(num_tracks),
+                                            _t(status), _t(ldmk_flags), _t(f_q), _t(covis)), "map_covisibility")
+
+    def ba_window_select(self, covis, f_q, status, win_frames, win_count, pose_fixed, f_count=None, eligible=None,
+                         params=None):
+        """Device tensors: covis [B, F], f_q / status [B], eligible [B, F] int32 or None -> win_frames
+        [B, W] (ascending frames, the tail -1), win_count [B], pose_fixed [B, W] int32: the W - 1 most
+        covisible frames and f_q, the n_fixed oldest of them held."""
+        B, F = covis.shape
+        W = win_frames.shape[1]
+        assert pose_fixed.shape == (B, W) and (eligible is None or eligible.shape == (B, F))
+        p = params or ba_window_params()
+        check(lib().mv_ba_window_select_dev(self.h, ctypes.byref(p), B, F, F if f_count is None else int(f_count), W,
+                                            _t(covis), _t(f_q), _t(status), _t(eligible), _t(win_frames),
+                                            _t(win_count), _t(pose_fixed)), "ba_window_select")
+
+    def ba_window_factors(self, kp, poses, cameras, track_id, num_tracks, ldmk_flags, win_frames, win_obs, ldmk_id,
+                          pose_id, meas, pose_offsets, status, poses_w, cameras_w, f_count=None, params=None):
+        """Device tensors: kp [B, F, cap, 2], poses [B, F, 7], cameras [B, F, 4], the map state and
+        win_frames [B, W] -> win_obs [B, track_cap], the factor list of ba_solve with frames = W (ldmk_id /
+        pose_id [factor_cap], meas [factor_cap, 2], pose_offsets [B * W + 1], status [1]) and poses_w
+        [B, W, 7], cameras_w [B, W, 4]."""
+        B, F, cap = track_id.shape
+        W = win_frames.shape[1]
+        assert kp.shape == (B, F, cap, 2) and poses_w.shape == (B, W, 7) and cameras_w.shape == (B, W, 4)
+        assert win_obs.shape == ldmk_flags.shape and pose_offsets.shape == (B * W + 1,)
+        p = params or ba_window_params()
+        check(lib().mv_ba_window_factors_dev(self.h, ctypes.byref(p), B, F, cap, ldmk_flags.shape[1],
+                                             F if f_count is None else int(f_count), W, ldmk_id.shape[0], _t(kp),
+                                             _t(poses), _t(cameras), _t(track_id), _t(num_tracks), _t(ldmk_flags),
+                                             _t(win_frames), _t(win_obs), _t(ldmk_id), _t(pose_id), _t(meas),
+                                             _t(pose_offsets), _t(status), _t(poses_w), _t(cameras_w)),
+              "ba_window_factors")
+
+    def ba_window_scatter(self, win_frames, poses_w, poses, f_count=None):
+        """Device tensors: win_frames [B, W], poses_w [B, W, 7] (ba_solve's poses_out) -> poses [B, F, 7],
+        the window's frames overwritten in place, every other pose untouched."""
+        B, F = poses.shape[0], poses.shape[1]
+        W = win_frames.shape[1]
+        assert poses_w.shape == (B, W, 7) and win_frames.shape[0] == B
+        check(lib().mv_ba_window_scatter_dev(self.h, B, F, F if f_count is None else int(f_count), W, _t(win_frames),
+                                             _t(poses_w), _t(poses)), "ba_window_scatter")
 
     # ---------------- loop closure (include/loop_closure.h) ----------------
     def bow_words(self, voc, desc_scales, desc, num_sel, patches, base, wid, word_id, best_match, scores=None):
