@@ -20,6 +20,8 @@
 //     (f) candidate landmarks and poses (rounded once to fp32) into the slab, the candidate's cost.
 //     (g) thread 0 decides and broadcasts through LDS; an accepted candidate is copied to the output.
 //   After a rejected step the linearisation is kept: at the same fp32 state it is the same bits.
+// The loss, the cost tree, the pose retraction and the decision are mv_lm.hpp's, shared with
+// k_pg_solve and k_pnp_solve; the linearisation, the Schur solve and the state copy are this file's.
 // All arithmetic is float64 in the order of tests/lba_reference.py (-ffp-contract=off).  LDS:
 // ((6F + 1)(6F + 2) / 2 + 6F) doubles, 38.8 KiB at 16 poses, 4.0 KiB at 5 -- the triangle only,
 // so that small windows share a CU -- plus 2 KiB for the cost tree.
@@ -30,9 +32,13 @@
 
 #include "bundle_adjust.h"
 #include "mv_internal.hpp"
+#include "mv_lm.hpp"
 #include "pf_linearize.hpp"
 
 namespace {
+
+using mv::dmax;
+using mv::tri;
 
 constexpr int NT = 256;
 constexpr int MAXP = MV_BA_MAX_POSES;
@@ -67,24 +73,6 @@ __host__ __device__ inline size_t ba_lds_doubles(int F) {
     return (n + 1) * (n + 2) / 2 + n;
 }
 
-__device__ __forceinline__ int tri(int i, int j) { return i * (i + 1) / 2 + j; }  // i >= j
-
-__device__ __forceinline__ double dmax(double a, double b) { return a > b ? a : b; }
-
-__device__ __forceinline__ void rot(const double *q, double *R) {  // k_pf_linearize's polynomial
-    const double w = q[0], x = q[1], y = q[2], z = q[3];
-    const double ww = w * w, xx = x * x, yy = y * y, zz = z * z;
-    R[0] = ((ww + xx) - yy) - zz;
-    R[1] = 2.0 * (x * y - w * z);
-    R[2] = 2.0 * (x * z + w * y);
-    R[3] = 2.0 * (x * y + w * z);
-    R[4] = ((ww - xx) + yy) - zz;
-    R[5] = 2.0 * (y * z - w * x);
-    R[6] = 2.0 * (x * z - w * y);
-    R[7] = 2.0 * (y * z + w * x);
-    R[8] = ((ww - xx) - yy) + zz;
-}
-
 // the window's view of one workgroup
 struct Win {
     int s, F, cap, o0, nf;
@@ -109,12 +97,8 @@ __device__ void linearize(const Win &W, const float *poses, const float *ldmk, b
         mv::pf_linearize(ldmk + 3l * t, poses + 7l * f, W.cams + 4l * p, W.meas[2 * g], W.meas[2 * g + 1], jac, J);
         const double e0 = (double)J[18], e1 = (double)J[19];
         const double s = e0 * e0 + e1 * e1;
-        double rho = s, wt = 1.0;
-        if (huber > 0.0) {
-            const double r = sqrt(s);
-            if (!(s <= huber * huber)) rho = (2.0 * huber) * r - huber * huber;
-            if (!(r <= huber)) wt = huber / r;
-        }
+        double rho, wt;
+        mv::huber_loss(s, huber, rho, wt);
         part = part + rho;
         if (jac) {
             float4 *o = reinterpret_cast<float4 *>(W.J + 20l * k);
@@ -123,14 +107,7 @@ __device__ void linearize(const Win &W, const float *poses, const float *ldmk, b
             W.w[k] = wt;
         }
     }
-    s_part[tid] = part;
-    __syncthreads();
-    if (tid == 0) {
-        double c = 0.0;
-        for (int i = 0; i < NT; i++) c = c + s_part[i];
-        *out = c;
-    }
-    __syncthreads();
+    mv::tree_sum_256(part, s_part, out);
 }
 
 __global__ __launch_bounds__(NT) void k_ba_solve(mv_ba_params P, int batch, int F, int cap, int num_factors, int fcap,
@@ -143,8 +120,9 @@ __global__ __launch_bounds__(NT) void k_ba_solve(mv_ba_params P, int batch, int 
     extern __shared__ double s_dyn[];  // the packed triangle [n + 1 rows], then x [n]
     __shared__ double s_part[NT];
     __shared__ int s_off[MAXP + 1], s_fidx[MAXP], s_fpose[MAXP];
-    __shared__ int s_held[MAXP], s_stop, s_relin, s_fail, s_acc, s_iters;
-    __shared__ double s_lambda, s_cost, s_cand;
+    __shared__ int s_held[MAXP], s_fail, s_iters;
+    __shared__ mv::LmState s_lm;
+    __shared__ double s_cand;
     const int tid = threadIdx.x;
     const size_t wg = blockIdx.x;
     float *const Jf = scr.J + wg * (size_t)fcap * 20;
@@ -198,9 +176,8 @@ __global__ __launch_bounds__(NT) void k_ba_solve(mv_ba_params P, int batch, int 
         if (tid < F)
             s_held[tid] = (fixed ? fixed[(size_t)s * F + tid] != 0 : tid == 0) || s_off[tid + 1] == s_off[tid];
         if (tid == 0) {
-            s_lambda = P.lambda_init;
-            s_stop = 0, s_relin = 0, s_fail = 0, s_acc = 0, s_iters = 0;
-            s_cost = 0.0;
+            mv::lm_reset(s_lm, P.lambda_init);
+            s_fail = 0, s_iters = 0;
         }
         __syncthreads();
         int nfree = 0;
@@ -226,13 +203,13 @@ __global__ __launch_bounds__(NT) void k_ba_solve(mv_ba_params P, int batch, int 
 
         Win W{s, F, cap, o0, nf, cams, lid, pid, meas, Jf, wf};
         double *const Lm = s_dyn, *const xs = s_dyn + (n + 1) * (n + 2) / 2;
-        linearize(W, Po, Lo, true, P.huber_px, s_part, &s_cost);
-        const double c_init = s_cost;
+        linearize(W, Po, Lo, true, P.huber_px, s_part, &s_lm.cost);
+        const double c_init = s_lm.cost;
 
         for (int it = 0; it < P.max_iters; it++) {
-            if (s_stop) break;  // uniform: written before the last barrier
-            if (s_relin) linearize(W, Po, Lo, true, P.huber_px, s_part, &s_cost);
-            const double lam = s_lambda, floor_ = P.diag_floor;
+            if (s_lm.stop) break;  // uniform: written before the last barrier
+            if (s_lm.relin) linearize(W, Po, Lo, true, P.huber_px, s_part, &s_lm.cost);
+            const double lam = s_lm.lambda, floor_ = P.diag_floor;
 
             // (b) landmarks
             for (int t = tid; t < cap; t += NT) {
@@ -425,47 +402,18 @@ __global__ __launch_bounds__(NT) void k_ba_solve(mv_ba_params P, int batch, int 
                     for (int c = 0; c < 7; c++) cP[7 * f + c] = Po[7 * f + c];
                     continue;
                 }
-                const double *d = xs + 6 * fi;
-                const double h0 = 0.5 * d[0], h1 = 0.5 * d[1], h2 = 0.5 * d[2];
-                const double nn = sqrt(((1.0 + h0 * h0) + h1 * h1) + h2 * h2);
-                const double a[4] = {1.0 / nn, h0 / nn, h1 / nn, h2 / nn};
-                const double b[4] = {Po[7 * f], Po[7 * f + 1], Po[7 * f + 2], Po[7 * f + 3]};
-                const double t0 = Po[7 * f + 4], t1 = Po[7 * f + 5], t2 = Po[7 * f + 6];
-                const double o0_ = ((a[0] * b[0] - a[1] * b[1]) - a[2] * b[2]) - a[3] * b[3];
-                const double o1_ = ((a[0] * b[1] + a[1] * b[0]) + a[2] * b[3]) - a[3] * b[2];
-                const double o2_ = ((a[0] * b[2] - a[1] * b[3]) + a[2] * b[0]) + a[3] * b[1];
-                const double o3_ = ((a[0] * b[3] + a[1] * b[2]) - a[2] * b[1]) + a[3] * b[0];
-                const double mm = sqrt(((o0_ * o0_ + o1_ * o1_) + o2_ * o2_) + o3_ * o3_);
-                double R[9];
-                rot(a, R);
-                cP[7 * f] = (float)(o0_ / mm);
-                cP[7 * f + 1] = (float)(o1_ / mm);
-                cP[7 * f + 2] = (float)(o2_ / mm);
-                cP[7 * f + 3] = (float)(o3_ / mm);
-                cP[7 * f + 4] = (float)(((R[0] * t0 + R[1] * t1) + R[2] * t2) + d[3]);
-                cP[7 * f + 5] = (float)(((R[3] * t0 + R[4] * t1) + R[5] * t2) + d[4]);
-                cP[7 * f + 6] = (float)(((R[6] * t0 + R[7] * t1) + R[8] * t2) + d[5]);
+                mv::retract_pose(xs + 6 * fi, Po + 7 * f, cP + 7 * f);
             }
             __syncthreads();
             linearize(W, cP, cX, false, P.huber_px, s_part, &s_cand);
             // (g) the decision
             if (tid == 0) {
-                const double cur = s_cost, cand = s_cand;
                 s_iters = s_iters + 1;
-                if (!s_fail && isfinite(cand) && cand < cur) {
-                    if (cur - cand < P.rel_tol * cur) s_stop = 1;
-                    s_cost = cand;
-                    s_lambda = dmax(lam * P.lambda_down, P.lambda_min);
-                    s_relin = 1, s_acc = 1;
-                } else {
-                    s_lambda = lam * P.lambda_up;
-                    if (s_lambda > P.lambda_max) s_stop = 1;
-                    s_relin = 0, s_acc = 0;
-                }
+                mv::lm_decide(P, s_lm, s_fail != 0, s_cand);
                 s_fail = 0;
             }
             __syncthreads();
-            if (s_acc) {
+            if (s_lm.acc) {
                 for (int i = tid; i < F * 7; i += NT) Po[i] = cP[i];
                 for (int i = tid; i < cap * 3; i += NT) Lo[i] = cX[i];
             }
@@ -475,25 +423,16 @@ __global__ __launch_bounds__(NT) void k_ba_solve(mv_ba_params P, int batch, int 
             status[s] = MV_OK;
             iters[s] = s_iters;
             cost0[s] = c_init;
-            cost1[s] = s_cost;
+            cost1[s] = s_lm.cost;
         }
     }
 }
-
-bool in_range(double v, double lo, double hi) { return isfinite(v) && v >= lo && v <= hi; }
 
 }  // namespace
 
 extern "C" void mv_ba_params_default(mv_ba_params *p) {
     if (!p) return;
-    p->max_iters = 10;
-    p->lambda_init = 1e-4;
-    p->lambda_up = 10.0;
-    p->lambda_down = 0.1;
-    p->lambda_min = 1e-10;
-    p->lambda_max = 1e10;
-    p->diag_floor = 1e-6;
-    p->rel_tol = 1e-6;
+    mv::lm_params_default(p);
     p->huber_px = 0.0;
 }
 
@@ -506,28 +445,15 @@ extern "C" int mv_ba_solve_dev(mv_context *ctx, const mv_ba_params *p, int batch
     MV_REQUIRE(num_factors >= 0 && poses_in && landmarks_in && cameras && pose_offsets && poses_out && landmarks_out);
     MV_REQUIRE(num_factors == 0 || (ldmk_id && pose_id && meas));
     MV_REQUIRE(cost_initial && cost_final && iters && status);
-    MV_REQUIRE(p->max_iters >= 0 && p->max_iters <= 1000);
-    const double big = 1e300;
-    MV_REQUIRE(in_range(p->lambda_init, 0.0, big) && p->lambda_init > 0.0);
-    MV_REQUIRE(in_range(p->lambda_up, 1.0, big) && in_range(p->lambda_down, 0.0, 1.0) && p->lambda_down > 0.0);
-    MV_REQUIRE(in_range(p->lambda_min, 0.0, big) && in_range(p->lambda_max, p->lambda_min, big));
-    MV_REQUIRE(in_range(p->diag_floor, 0.0, big) && in_range(p->rel_tol, 0.0, big) && in_range(p->huber_px, 0.0, big));
+    MV_REQUIRE(mv::lm_params_ok(*p, p->huber_px));
     MV_REQUIRE((long)batch * frames < (1l << 31) && (long)batch * track_cap < (1l << 31));
     MV_REQUIRE((long)frames * track_cap < (1l << 31));
     const size_t lds = ba_lds_doubles(frames) * sizeof(double);
     MV_REQUIRE(lds <= 62 * 1024);  // with the 2 KiB cost tree: what a workgroup gets without asking for more
     MV_HIP_TRY(hipSetDevice(ctx->device));
-    // two workgroups per CU, fewer when their slabs together would pass 2 GiB of scratch (the windows
-    // then queue on the workgroups there are); MV_BA_GRID (tests): another workgroup count -- more
-    // windows than workgroups, slabs reused
     const long fcap = std::min<long>((long)frames * track_cap, num_factors);
     const size_t slab = mv::carve_bytes(ba_scratch_layout, (size_t)1, (size_t)fcap, (size_t)track_cap, (size_t)frames);
-    const long fit = std::max<long>(1, (long)(((size_t)2 << 30) / slab));
-    int grid = (int)std::min<long>(std::min<long>(batch, 2l * std::max(ctx->cu_count, 1)), fit);
-    if (const char *e = getenv("MV_BA_GRID")) {
-        const int g = atoi(e);
-        if (g > 0) grid = std::min(batch, g);
-    }
+    const int grid = mv::solver_grid(ctx, batch, slab, "MV_BA_GRID");
     BaScratch m;
     if (!mv::carve(mv::scratch, ctx, [&](mv::Carve &c) {
             m = ba_scratch_layout(c, (size_t)grid, (size_t)fcap, (size_t)track_cap, (size_t)frames);

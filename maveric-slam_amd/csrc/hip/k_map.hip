@@ -22,9 +22,10 @@
 //              tile in one work list (LDS, 2048 entries at a time), so the exact dots -- 1 KiB row
 //              gathers, latency-bound -- run one per thread whatever the spread of candidates.
 //     fold     the owner folds its candidates' scores into best and second best (ap_exact::better).
-//   claim      k_tr_claim's keys: (score as an ordered u32) << 32 | ~l, one LDS atomicMax per
-//              proposing landmark over `cap` keys; a landmark that is not named has no match.
-//   emit       k_pnp_gather's ballot compaction in ascending l.
+//   claim      k_tr_claim's keys (tr_claim.hpp): (score as an ordered u32) << 32 | ~l, one LDS
+//              atomicMax per proposing landmark over `cap` keys; a landmark that is not named has
+//              no match.
+//   emit       the ballot compaction of tr::block_rank in ascending l.
 //   The proposals wait in match_idx / match_score between the stages; a thread reads back only what
 //   it wrote itself (landmark l is always thread l % 256's).
 // All arithmetic is in the order of tests/map_reference.py (-ffp-contract=off).
@@ -38,8 +39,13 @@
 #include "ap_exact.hpp"
 #include "map_match.h"
 #include "mv_internal.hpp"
+#include "mv_lm.hpp"
+#include "tr_claim.hpp"
+#include "tr_scan.hpp"
 
 namespace {
+
+using tr::clampn;
 
 constexpr int NT = 256;
 constexpr int KD = 256;             // descriptor length
@@ -53,15 +59,6 @@ struct MapGrid {
     int gx, gy;
 };
 
-__device__ __forceinline__ int clampn(int v, int cap) { return v < 0 ? 0 : (v > cap ? cap : v); }
-
-// fp32 -> u32 with the order of `<` on non-NaN values (k_tracks.hip's)
-__device__ __forceinline__ unsigned ordered_bits(float f) {
-    if (f == 0.f) f = 0.f;
-    const unsigned u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 // the cell of a finite coordinate along an axis of g cells
 __device__ __forceinline__ int cell_of(double x, double side, int g) {
     double q = floor(x / side);
@@ -69,20 +66,6 @@ __device__ __forceinline__ int cell_of(double x, double side, int g) {
     q = q < 0.0 ? 0.0 : q;
     q = q > hi ? hi : q;
     return (int)q;
-}
-
-// inclusive scan of one int per thread over the workgroup (Hillis-Steele in s_scan); ends with a barrier
-__device__ __forceinline__ int block_scan(int v, int *s_scan) {
-    const int tid = threadIdx.x;
-    s_scan[tid] = v;
-    __syncthreads();
-    for (int off = 1; off < NT; off <<= 1) {
-        const int add = tid >= off ? s_scan[tid - off] : 0;
-        __syncthreads();
-        s_scan[tid] += add;
-        __syncthreads();
-    }
-    return s_scan[tid];
 }
 
 // f(j) for every candidate j of the projection (u, v): the exact disc test over the 3 x 3 cells
@@ -120,7 +103,7 @@ __global__ __launch_bounds__(NT) void k_map_match(mv_map_params P, MapGrid G, in
     __shared__ unsigned short s_wj[WL]; // the keypoint
     __shared__ unsigned char s_wl[WL];  // and the landmark's thread
     __shared__ int s_scan[NT], s_wc[NT / 64], s_m;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int ncell = G.gx * G.gy;
     const double r2 = P.radius_px * P.radius_px;
 
@@ -159,7 +142,7 @@ __global__ __launch_bounds__(NT) void k_map_match(mv_map_params P, MapGrid G, in
                 cnt[k] = c < ncell ? s_fill[c] : 0;
                 sum += cnt[k];
             }
-            int run = block_scan(sum, s_scan) - sum;
+            int run = tr::scan_inclusive_256(sum, s_scan) - sum;
 #pragma unroll
             for (int k = 0; k < NCELL / NT; k++) {
                 const int c = tid * (NCELL / NT) + k;
@@ -175,7 +158,7 @@ __global__ __launch_bounds__(NT) void k_map_match(mv_map_params P, MapGrid G, in
         }
         __syncthreads();
 
-        // ---- the pose: R of the promoted quaternion (k_pf_linearize's polynomial), t, the camera ----
+        // ---- the pose: R of the promoted quaternion (mv::quat_rot), t, the camera ----
         double q[7], K[4];
         bool pose_ok = true;
 #pragma unroll
@@ -185,13 +168,8 @@ __global__ __launch_bounds__(NT) void k_map_match(mv_map_params P, MapGrid G, in
         }
 #pragma unroll
         for (int i = 0; i < 4; i++) K[i] = (double)cams[(size_t)s * 4 + i];
-        const double ww = q[0] * q[0], xx = q[1] * q[1], yy = q[2] * q[2], zz = q[3] * q[3];
-        const double R0 = ((ww + xx) - yy) - zz, R1 = 2.0 * (q[1] * q[2] - q[0] * q[3]),
-                     R2 = 2.0 * (q[1] * q[3] + q[0] * q[2]);
-        const double R3 = 2.0 * (q[1] * q[2] + q[0] * q[3]), R4 = ((ww - xx) + yy) - zz,
-                     R5 = 2.0 * (q[2] * q[3] - q[0] * q[1]);
-        const double R6 = 2.0 * (q[1] * q[3] - q[0] * q[2]), R7 = 2.0 * (q[2] * q[3] + q[0] * q[1]),
-                     R8 = ((ww - xx) - yy) + zz;
+        double R[9];
+        mv::quat_rot(q, R);
 
         // ---- project, list, score and fold, a tile of 256 landmarks at a time ----
         for (int base = 0; base < L; base += NT) {
@@ -201,9 +179,9 @@ __global__ __launch_bounds__(NT) void k_map_match(mv_map_params P, MapGrid G, in
             if (l < nl && pose_ok) {
                 if (fl[l] == 0) {
                     const double X0 = (double)X[3l * l], X1 = (double)X[3l * l + 1], X2 = (double)X[3l * l + 2];
-                    const double px = ((R0 * X0 + R1 * X1) + R2 * X2) + q[4];
-                    const double py = ((R3 * X0 + R4 * X1) + R5 * X2) + q[5];
-                    const double pz = ((R6 * X0 + R7 * X1) + R8 * X2) + q[6];
+                    const double px = ((R[0] * X0 + R[1] * X1) + R[2] * X2) + q[4];
+                    const double py = ((R[3] * X0 + R[4] * X1) + R[5] * X2) + q[5];
+                    const double pz = ((R[6] * X0 + R[7] * X1) + R[8] * X2) + q[6];
                     u = K[0] * (px / pz) + K[2];
                     v = K[1] * (py / pz) + K[3];
                     vis = isfinite(X0) && isfinite(X1) && isfinite(X2) && isfinite(u) && isfinite(v) &&
@@ -217,7 +195,7 @@ __global__ __launch_bounds__(NT) void k_map_match(mv_map_params P, MapGrid G, in
                 o_proj[2l * l + 1] = vis ? (float)v : 0.f;
                 o_ncand[l] = vis ? c : -1;
             }
-            const int end = block_scan(c, s_scan), off = end - c;
+            const int end = tr::scan_inclusive_256(c, s_scan), off = end - c;
             const int total = s_scan[NT - 1];
             __syncthreads();  // read before the next scan writes it
             float b1 = -__builtin_inff(), b2 = 0.f;
@@ -271,12 +249,12 @@ __global__ __launch_bounds__(NT) void k_map_match(mv_map_params P, MapGrid G, in
         // ---- claim: a keypoint accepts the greatest (score, lowest l) ----
         for (int l = tid; l < L; l += NT) {
             const int j = o_idx[l];
-            if (j >= 0) atomicMax(&s_key[j], ((unsigned long long)ordered_bits(o_score[l]) << 32) | (unsigned)~l);
+            if (j >= 0) atomicMax(&s_key[j], tr::claim_key(tr::ordered_bits(o_score[l]), l));
         }
         __syncthreads();
         for (int l = tid; l < L; l += NT) {
             const int j = o_idx[l];
-            if (j >= 0 && (unsigned)s_key[j] != (unsigned)~l) o_idx[l] = -1, o_score[l] = 0.f;
+            if (j >= 0 && !tr::claim_won(s_key[j], l)) o_idx[l] = -1, o_score[l] = 0.f;
         }
 
         // ---- emit the pairs in ascending l ----
@@ -284,11 +262,7 @@ __global__ __launch_bounds__(NT) void k_map_match(mv_map_params P, MapGrid G, in
             const int l = base + tid;
             const int j = l < L ? o_idx[l] : -1;
             const bool valid = j >= 0;
-            const unsigned long long bal = __ballot(valid);
-            if (lane == 0) s_wc[wave] = __popcll(bal);
-            __syncthreads();
-            int off = s_m + __popcll(bal & ((1ull << lane) - 1ull));
-            for (int w = 0; w < wave; w++) off += s_wc[w];
+            const int off = s_m + tr::block_rank(valid, s_wc);
             if (valid && off < cap) {  // off < nn always: a keypoint accepts one landmark
                 o3[3l * off] = X[3l * l], o3[3l * off + 1] = X[3l * l + 1], o3[3l * off + 2] = X[3l * l + 2];
                 o2[2l * off] = s_kp[j].x, o2[2l * off + 1] = s_kp[j].y;
@@ -395,13 +369,7 @@ extern "C" int mv_map_match_dev(mv_context *ctx, const mv_map_params *p, int bat
     if (!isfinite(G.side)) G.side = p->radius_px;  // a radius near DBL_MAX: one cell holds everything
     G.gx = (int)std::min<double>(GMAX, std::max(1.0, ceil(w / G.side)));
     G.gy = (int)std::min<double>(GMAX, std::max(1.0, ceil(h / G.side)));
-    // two workgroups per CU (the problems queue on the workgroups there are); MV_MAP_GRID (tests):
-    // another workgroup count
-    int grid = (int)std::min<long>(batch, 2l * std::max(ctx->cu_count, 1));
-    if (const char *e = getenv("MV_MAP_GRID")) {
-        const int g = atoi(e);
-        if (g > 0) grid = std::min(batch, g);
-    }
+    const int grid = mv::solver_grid(ctx, batch, 0, "MV_MAP_GRID");  // no slab: LDS only
     MV_LAUNCH("k_map_match", k_map_match, dim3((unsigned)grid), dim3(NT), 0, ctx->stream, *p, G, batch, L, cap, n_ldmk,
               landmarks, ldmk_flags, ldmk_desc, pose_prior, cameras, n_new, kp_new, desc_new, proj, ncand, match_idx,
               match_score, pts3, pts2, pair_ldmk, count);

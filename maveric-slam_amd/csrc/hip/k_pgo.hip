@@ -30,6 +30,8 @@
 //         divides (the products are rounded on their own, so this is the serial sum's bits).
 //     (d) candidate poses (rounded once to fp32) into the slab, the candidate's cost.
 //     (e) thread 0 decides and broadcasts through LDS; an accepted candidate is copied to the output.
+// The loss, the cost tree, the pose retraction and the decision are mv_lm.hpp's, shared with
+// k_ba_solve and k_pnp_solve; the prologue's scans are tr_scan.hpp's, a barrier after each.
 // All arithmetic is float64 in the order of tests/pgo_reference.py (-ffp-contract=off).
 // The factor lives in the slab (env_cap x 36 doubles) and every block column goes through it: one
 // read and one write of the slab per phase.  LDS holds b / y / x and the back substitution's
@@ -45,10 +47,15 @@
 #include <algorithm>
 
 #include "mv_internal.hpp"
+#include "mv_lm.hpp"
 #include "mv_quat.hpp"
 #include "pose_graph.h"
+#include "tr_scan.hpp"
 
 namespace {
+
+using mv::dmax;
+using mv::qmul;
 
 constexpr int NT = 256;
 
@@ -93,29 +100,6 @@ PgScratch pg_scratch_layout(mv::Carve &c, size_t grid, size_t ecap, size_t envc,
     return m;
 }
 
-__device__ __forceinline__ double dmax(double a, double b) { return a > b ? a : b; }
-
-__device__ __forceinline__ void rot(const double *q, double *R) {  // k_pf_linearize's polynomial
-    const double w = q[0], x = q[1], y = q[2], z = q[3];
-    const double ww = w * w, xx = x * x, yy = y * y, zz = z * z;
-    R[0] = ((ww + xx) - yy) - zz;
-    R[1] = 2.0 * (x * y - w * z);
-    R[2] = 2.0 * (x * z + w * y);
-    R[3] = 2.0 * (x * y + w * z);
-    R[4] = ((ww - xx) + yy) - zz;
-    R[5] = 2.0 * (y * z - w * x);
-    R[6] = 2.0 * (x * z - w * y);
-    R[7] = 2.0 * (y * z + w * x);
-    R[8] = ((ww - xx) - yy) + zz;
-}
-
-__device__ __forceinline__ void qmul(const double *a, const double *b, double *o) {
-    o[0] = ((a[0] * b[0] - a[1] * b[1]) - a[2] * b[2]) - a[3] * b[3];
-    o[1] = ((a[0] * b[1] + a[1] * b[0]) + a[2] * b[3]) - a[3] * b[2];
-    o[2] = ((a[0] * b[2] - a[1] * b[3]) + a[2] * b[0]) + a[3] * b[1];
-    o[3] = ((a[0] * b[3] + a[1] * b[2]) - a[2] * b[1]) + a[3] * b[0];
-}
-
 // x, y: columns of a row-major 6 x 12 Jacobian (stride 12), or y = the error (stride 1)
 __device__ __forceinline__ double dot6(const double *x, const double *y, int ystride) {
     return ((((x[0] * y[0] + x[12] * y[ystride]) + x[24] * y[2 * ystride]) + x[36] * y[3 * ystride]) +
@@ -133,7 +117,7 @@ __device__ void edge_residual(const float *pi, const float *pj, int kind, const 
     const double ci[4] = {qi[0], -qi[1], -qi[2], -qi[3]}, cz[4] = {qz[0], -qz[1], -qz[2], -qz[3]};
     double qp[4], R[9], qe[4];
     qmul(qj, ci, qp);
-    rot(qp, R);
+    mv::quat_rot(qp, R);
     const double tp[3] = {tj[0] - ((R[0] * ti[0] + R[1] * ti[1]) + R[2] * ti[2]),
                           tj[1] - ((R[3] * ti[0] + R[4] * ti[1]) + R[5] * ti[2]),
                           tj[2] - ((R[6] * ti[0] + R[7] * ti[1]) + R[8] * ti[2])};
@@ -204,12 +188,8 @@ __device__ void linearize(const Gr &G, const float *poses, bool jac, double hube
         edge_residual(poses + 7l * i, poses + 7l * j, G.kind[g], G.z + 7 * g, G.w + 2 * g, e,
                       jac ? G.A + 72 * (size_t)k : nullptr);
         const double s = ((((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]) + e[3] * e[3]) + e[4] * e[4]) + e[5] * e[5];
-        double rho = s, wt = 1.0;
-        if (huber > 0.0) {
-            const double r = sqrt(s);
-            if (!(s <= huber * huber)) rho = (2.0 * huber) * r - huber * huber;
-            if (!(r <= huber)) wt = huber / r;
-        }
+        double rho, wt;
+        mv::huber_loss(s, huber, rho, wt);
         part = part + rho;
         if (jac) {
 #pragma unroll
@@ -217,40 +197,7 @@ __device__ void linearize(const Gr &G, const float *poses, bool jac, double hube
             G.wt[k] = wt;
         }
     }
-    s_part[tid] = part;
-    __syncthreads();
-    if (tid == 0) {
-        double c = 0.0;
-        for (int i = 0; i < NT; i++) c = c + s_part[i];
-        *out = c;
-    }
-    __syncthreads();
-}
-
-// Exclusive scan of v[0 .. n) in place by the whole workgroup; returns the total.  The caller has
-// put a barrier after the writes of v; ends with a barrier.
-__device__ int block_exscan(int *v, int n, int *s_scan) {
-    const int tid = threadIdx.x;
-    const int per = (n + NT - 1) / NT, b0 = min(n, tid * per), b1 = min(n, b0 + per);
-    int sum = 0;
-    for (int i = b0; i < b1; i++) sum += v[i];
-    s_scan[tid] = sum;
-    __syncthreads();
-    for (int d = 1; d < NT; d <<= 1) {
-        const int add = tid >= d ? s_scan[tid - d] : 0;
-        __syncthreads();
-        s_scan[tid] += add;
-        __syncthreads();
-    }
-    int run = s_scan[tid] - sum;
-    const int total = s_scan[NT - 1];
-    for (int i = b0; i < b1; i++) {
-        const int x = v[i];
-        v[i] = run;
-        run += x;
-    }
-    __syncthreads();
-    return total;
+    mv::tree_sum_256(part, s_part, out);
 }
 
 __global__ __launch_bounds__(NT) void k_pg_solve(mv_pg_params P, int batch, int N, int num_edges, int env_cap,
@@ -267,8 +214,9 @@ __global__ __launch_bounds__(NT) void k_pg_solve(mv_pg_params P, int batch, int 
     extern __shared__ double s_dyn[];
     __shared__ double s_part[NT];
     __shared__ int s_scan[NT];
-    __shared__ int s_e0, s_e1, s_stop, s_relin, s_fail, s_acc, s_iters;
-    __shared__ double s_lambda, s_cost, s_cand;
+    __shared__ int s_e0, s_e1, s_fail, s_iters;
+    __shared__ mv::LmState s_lm;
+    __shared__ double s_cand;
     const int tid = threadIdx.x;
     const size_t wg = blockIdx.x;
     double *const env = scr.env + wg * (size_t)envc * 36;
@@ -304,9 +252,8 @@ __global__ __launch_bounds__(NT) void k_pg_solve(mv_pg_params P, int batch, int 
         __syncthreads();  // the previous graph's shared state is done with
         if (tid == 0) {
             s_e0 = offs[s], s_e1 = offs[s + 1];
-            s_lambda = P.lambda_init;
-            s_stop = 0, s_relin = 0, s_fail = 0, s_acc = 0, s_iters = 0;
-            s_cost = 0.0;
+            mv::lm_reset(s_lm, P.lambda_init);
+            s_fail = 0, s_iters = 0;
         }
         const float *Pi = pin + (size_t)s * N * 7;
         float *Po = pout + (size_t)s * N * 7;
@@ -345,7 +292,8 @@ __global__ __launch_bounds__(NT) void k_pg_solve(mv_pg_params P, int batch, int 
             }
             if (tid == 0) nodeoff[N] = 0;
             __syncthreads();
-            block_exscan(nodeoff, N + 1, s_scan);
+            tr::scan_exclusive_256(N + 1, nodeoff, s_scan);
+            __syncthreads();
             for (int n = tid; n < N; n += NT) {
                 int p = nodeoff[n];
                 for (int k = 0; k < E; k++)
@@ -355,7 +303,8 @@ __global__ __launch_bounds__(NT) void k_pg_solve(mv_pg_params P, int batch, int 
                 fidx[n] = !held;
             }
             __syncthreads();
-            nfree = block_exscan(fidx, N, s_scan);
+            nfree = tr::scan_exclusive_256(N, fidx, s_scan);
+            __syncthreads();
             for (int n = tid; n < N; n += NT) {
                 if (colptr[n])
                     fnode[fidx[n]] = n;
@@ -379,7 +328,8 @@ __global__ __launch_bounds__(NT) void k_pg_solve(mv_pg_params P, int batch, int 
             }
             if (tid == 0) envoff[nfree] = 0;
             __syncthreads();
-            envtot = block_exscan(envoff, nfree + 1, s_scan);
+            envtot = tr::scan_exclusive_256(nfree + 1, envoff, s_scan);
+            __syncthreads();
             if (envtot > env_cap) st = MV_ERR_CAPACITY;  // envtot <= N (N + 1) / 2 <= envc otherwise
         }
         if (st != MV_OK || E == 0) {  // uniform
@@ -399,7 +349,8 @@ __global__ __launch_bounds__(NT) void k_pg_solve(mv_pg_params P, int batch, int 
         }
         if (tid == 0) colptr[nfree] = 0;
         __syncthreads();
-        block_exscan(colptr, nfree + 1, s_scan);  // total = envtot - nfree
+        tr::scan_exclusive_256(nfree + 1, colptr, s_scan);  // total = envtot - nfree
+        __syncthreads();
         for (int cb = tid; cb < nfree; cb += NT) {
             int p = colptr[cb];
             for (int kb = cb + 1; kb < nfree; kb++)
@@ -414,13 +365,13 @@ __global__ __launch_bounds__(NT) void k_pg_solve(mv_pg_params P, int batch, int 
 
         const int n = 6 * nfree;
         Gr G{base, e0, E, ei, ej, ekind, ez, ew, Af, evf, wf};
-        linearize(G, Po, true, P.huber, s_part, &s_cost);
-        const double c_init = s_cost;
+        linearize(G, Po, true, P.huber, s_part, &s_lm.cost);
+        const double c_init = s_lm.cost;
 
         for (int it = 0; it < P.max_iters; it++) {
-            if (s_stop) break;  // uniform: written before the last barrier
-            if (s_relin) linearize(G, Po, true, P.huber, s_part, &s_cost);
-            const double lam = s_lambda, floor_ = P.diag_floor;
+            if (s_lm.stop) break;  // uniform: written before the last barrier
+            if (s_lm.relin) linearize(G, Po, true, P.huber, s_part, &s_lm.cost);
+            const double lam = s_lm.lambda, floor_ = P.diag_floor;
 
             // (a) H inside the envelope and b
             for (int t = tid; t < envtot * 36; t += NT) {
@@ -577,44 +528,18 @@ __global__ __launch_bounds__(NT) void k_pg_solve(mv_pg_params P, int batch, int 
                     for (int c = 0; c < 7; c++) cP[7 * f + c] = Po[7 * f + c];
                     continue;
                 }
-                const double *d = xs + 6 * fi;
-                const double h0 = 0.5 * d[0], h1 = 0.5 * d[1], h2 = 0.5 * d[2];
-                const double nn = sqrt(((1.0 + h0 * h0) + h1 * h1) + h2 * h2);
-                const double a[4] = {1.0 / nn, h0 / nn, h1 / nn, h2 / nn};
-                const double b[4] = {Po[7 * f], Po[7 * f + 1], Po[7 * f + 2], Po[7 * f + 3]};
-                const double t0 = Po[7 * f + 4], t1 = Po[7 * f + 5], t2 = Po[7 * f + 6];
-                double o[4], R[9];
-                qmul(a, b, o);
-                const double mm = sqrt(((o[0] * o[0] + o[1] * o[1]) + o[2] * o[2]) + o[3] * o[3]);
-                rot(a, R);
-                cP[7 * f] = (float)(o[0] / mm);
-                cP[7 * f + 1] = (float)(o[1] / mm);
-                cP[7 * f + 2] = (float)(o[2] / mm);
-                cP[7 * f + 3] = (float)(o[3] / mm);
-                cP[7 * f + 4] = (float)(((R[0] * t0 + R[1] * t1) + R[2] * t2) + d[3]);
-                cP[7 * f + 5] = (float)(((R[3] * t0 + R[4] * t1) + R[5] * t2) + d[4]);
-                cP[7 * f + 6] = (float)(((R[6] * t0 + R[7] * t1) + R[8] * t2) + d[5]);
+                mv::retract_pose(xs + 6 * fi, Po + 7 * f, cP + 7 * f);
             }
             __syncthreads();
             linearize(G, cP, false, P.huber, s_part, &s_cand);
             // (e) the decision
             if (tid == 0) {
-                const double cur = s_cost, cand = s_cand;
                 s_iters = s_iters + 1;
-                if (!s_fail && isfinite(cand) && cand < cur) {
-                    if (cur - cand < P.rel_tol * cur) s_stop = 1;
-                    s_cost = cand;
-                    s_lambda = dmax(lam * P.lambda_down, P.lambda_min);
-                    s_relin = 1, s_acc = 1;
-                } else {
-                    s_lambda = lam * P.lambda_up;
-                    if (s_lambda > P.lambda_max) s_stop = 1;
-                    s_relin = 0, s_acc = 0;
-                }
+                mv::lm_decide(P, s_lm, s_fail != 0, s_cand);
                 s_fail = 0;
             }
             __syncthreads();
-            if (s_acc)
+            if (s_lm.acc)
                 for (int i = tid; i < N * 7; i += NT) Po[i] = cP[i];
             __syncthreads();
         }
@@ -622,7 +547,7 @@ __global__ __launch_bounds__(NT) void k_pg_solve(mv_pg_params P, int batch, int 
             status[s] = MV_OK;
             iters[s] = s_iters;
             cost0[s] = c_init;
-            cost1[s] = s_cost;
+            cost1[s] = s_lm.cost;
         }
     }
 }
@@ -642,20 +567,11 @@ __global__ void k_pg_edges_from_transforms(int E, const float *__restrict__ T, f
     for (int i = 0; i < 3; i++) z[7l * k + 4 + i] = (float)t[i];
 }
 
-bool in_range(double v, double lo, double hi) { return isfinite(v) && v >= lo && v <= hi; }
-
 }  // namespace
 
 extern "C" void mv_pg_params_default(mv_pg_params *p) {
     if (!p) return;
-    p->max_iters = 10;
-    p->lambda_init = 1e-4;
-    p->lambda_up = 10.0;
-    p->lambda_down = 0.1;
-    p->lambda_min = 1e-10;
-    p->lambda_max = 1e10;
-    p->diag_floor = 1e-6;
-    p->rel_tol = 1e-6;
+    mv::lm_params_default(p);
     p->huber = 0.0;
 }
 
@@ -667,28 +583,16 @@ extern "C" int mv_pg_solve_dev(mv_context *ctx, const mv_pg_params *p, int batch
     MV_REQUIRE(num_edges >= 0 && poses_in && edge_offsets && poses_out);
     MV_REQUIRE(num_edges == 0 || (edge_i && edge_j && edge_kind && edge_z && edge_w));
     MV_REQUIRE(cost_initial && cost_final && iters && status);
-    MV_REQUIRE(p->max_iters >= 0 && p->max_iters <= 1000);
-    const double big = 1e300;
-    MV_REQUIRE(in_range(p->lambda_init, 0.0, big) && p->lambda_init > 0.0);
-    MV_REQUIRE(in_range(p->lambda_up, 1.0, big) && in_range(p->lambda_down, 0.0, 1.0) && p->lambda_down > 0.0);
-    MV_REQUIRE(in_range(p->lambda_min, 0.0, big) && in_range(p->lambda_max, p->lambda_min, big));
-    MV_REQUIRE(in_range(p->diag_floor, 0.0, big) && in_range(p->rel_tol, 0.0, big) && in_range(p->huber, 0.0, big));
+    MV_REQUIRE(mv::lm_params_ok(*p, p->huber));
     MV_REQUIRE((long)batch * nodes < (1l << 31));
     const size_t lds = (size_t)12 * nodes * sizeof(double) + (size_t)(5 * nodes + 2) * sizeof(int);  // 58 KiB at 512
     MV_HIP_TRY(hipSetDevice(ctx->device));
-    // two workgroups per CU, fewer when their slabs together would pass 2 GiB of scratch (the graphs
-    // then queue on the workgroups there are); MV_PG_GRID (tests): another workgroup count -- more
-    // graphs than workgroups, slabs reused.  No envelope is larger than the full lower triangle.
+    // no envelope is larger than the full lower triangle
     const size_t ecap = (size_t)std::max(num_edges, 1);
     const size_t envc = (size_t)std::min<long>(env_cap, (long)nodes * (nodes + 1) / 2);
     const size_t slab = mv::carve_bytes(pg_scratch_layout, (size_t)2, ecap, envc, (size_t)nodes) -
                         mv::carve_bytes(pg_scratch_layout, (size_t)1, ecap, envc, (size_t)nodes);  // of one workgroup
-    const long fit = std::max<long>(1, (long)(((size_t)2 << 30) / slab));
-    int grid = (int)std::min<long>(std::min<long>(batch, 2l * std::max(ctx->cu_count, 1)), fit);
-    if (const char *e = getenv("MV_PG_GRID")) {
-        const int g = atoi(e);
-        if (g > 0) grid = std::min(batch, g);
-    }
+    const int grid = mv::solver_grid(ctx, batch, slab, "MV_PG_GRID");
     PgScratch m;
     if (!mv::carve(mv::scratch, ctx, [&](mv::Carve &c) { m = pg_scratch_layout(c, (size_t)grid, ecap, envc, (size_t)nodes); }))
         return MV_ERR_OUT_OF_MEMORY;

@@ -1,7 +1,7 @@
 // k_pnp.hip -- map localisation (include/absolute_pose.h): 3D-2D pairs gathered from the tracks,
 // then P3P RANSAC with preemptive scoring and a pose-only Levenberg-Marquardt refinement.
 //
-// k_pnp_gather: one workgroup per problem, one wave-ballot compaction per 256 rows.
+// k_pnp_gather: one workgroup per problem, one wave-ballot compaction (tr::block_rank) per 256 rows.
 // k_pnp_solve:  one 256-thread workgroup per problem, a grid-stride loop over the problems.
 //   stage      the valid pairs, promoted once to float64, into LDS (structure of arrays) by the same
 //              ballot compaction, with each pair's index in the input.
@@ -13,12 +13,13 @@
 //              wave from one LDS address (a broadcast).
 //   select     each owner ranks its (cost, h) key against the 257 keys in LDS; ranks 0..7 survive.
 //   full score a survivor at a time: thread t adds the pairs t, t + 256, ..., thread 0 adds the 256
-//              partials in ascending order (k_ba_solve's tree).
+//              partials in ascending order (the solvers' fixed tree, mv_lm.hpp).
 //   refine     per round: inlier flags in LDS, then the LM: thread t linearises its pairs
 //              (pf_linearize.hpp) and keeps 27 partial sums in registers, which go to a [27][256]
-//              slab of the context scratch; threads 0..26 add one entry each in ascending order;
-//              thread 0 damps, factors the 6 x 6 system in LDS (right-hand side as row 6), retracts
-//              and decides; the candidate's cost by the tree.
+//              slab of the context scratch; threads 0..26 add one entry each in ascending order
+//              between the tree's barriers; thread 0 damps, factors the 6 x 6 system in LDS
+//              (right-hand side as row 6), retracts and decides; the candidate's cost by the tree.
+//              Loss, tree, retraction and decision are mv_lm.hpp's, as in k_ba_solve and k_pg_solve.
 // All arithmetic is float64 in the order of tests/pnp_reference.py (-ffp-contract=off).
 // LDS: 45 B per pair of `cap` (dynamic) + 11.5 KiB (sum tree, keys, hypothesis poses, 6 x 6).
 #include <math.h>
@@ -28,10 +29,15 @@
 
 #include "absolute_pose.h"
 #include "mv_internal.hpp"
+#include "mv_lm.hpp"
 #include "mv_quat.hpp"
 #include "pf_linearize.hpp"
+#include "tr_claim.hpp"
 
 namespace {
+
+using mv::dmax;
+using mv::tri;
 
 constexpr int NT = 256;
 constexpr int NE = MV_PNP_MAX_HYPOTHESES + 1;  // hypothesis entries: 0 = the prior, e = h + 1
@@ -58,9 +64,6 @@ __device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
     return x ^ (x >> 31);
 }
 
-__device__ __forceinline__ int tri(int i, int j) { return i * (i + 1) / 2 + j; }  // i >= j
-__device__ __forceinline__ double dmax(double a, double b) { return a > b ? a : b; }
-
 struct V3 {
     double x, y, z;
 };
@@ -85,22 +88,13 @@ __device__ __forceinline__ V3 bearing(double u, double v, const Cam &K) {
     return {x / n, y / n, 1.0 / n};
 }
 
-// a pose as the scorer wants it: R of the promoted fp32 quaternion (k_pf_linearize's polynomial), t
+// a pose as the scorer wants it: R of the promoted fp32 quaternion (mv::quat_rot), t
 struct PoseRt {
     double R[9], t[3];
 };
 __device__ __forceinline__ void pose_rt(const float *p, PoseRt &P) {
-    const double w = p[0], x = p[1], y = p[2], z = p[3];
-    const double ww = w * w, xx = x * x, yy = y * y, zz = z * z;
-    P.R[0] = ((ww + xx) - yy) - zz;
-    P.R[1] = 2.0 * (x * y - w * z);
-    P.R[2] = 2.0 * (x * z + w * y);
-    P.R[3] = 2.0 * (x * y + w * z);
-    P.R[4] = ((ww - xx) + yy) - zz;
-    P.R[5] = 2.0 * (y * z - w * x);
-    P.R[6] = 2.0 * (x * z - w * y);
-    P.R[7] = 2.0 * (y * z + w * x);
-    P.R[8] = ((ww - xx) - yy) + zz;
+    const double q[4] = {p[0], p[1], p[2], p[3]};
+    mv::quat_rot(q, P.R);
     P.t[0] = p[4], P.t[1] = p[5], P.t[2] = p[6];
 }
 __device__ __forceinline__ void pair_err(const PoseRt &P, const Cam &K, double X0, double X1, double X2, double u,
@@ -249,15 +243,8 @@ __device__ void score_all(const Prob &Q, const float *pose, bool flags, unsigned
         if (flags) inl[k] = in ? 1 : 0;
         c += in ? 1 : 0;
     }
-    s_part[tid] = part;
     if (flags && c) atomicAdd(cnt, c);
-    __syncthreads();
-    if (tid == 0) {
-        double s = 0.0;
-        for (int i = 0; i < NT; i++) s = s + s_part[i];
-        *out = s;
-    }
-    __syncthreads();
+    mv::tree_sum_256(part, s_part, out);
 }
 
 // Linearise the inliers at `pose` [7]: the cost to *out by the tree; with jac the 27 sums of the
@@ -279,12 +266,8 @@ __device__ void linearize(const Prob &Q, const float *pose, const unsigned char 
         mv::pf_linearize(X, T, Q.Kf, (float)Q.U[k], (float)Q.V[k], jac, J);
         const double e0 = (double)J[18], e1 = (double)J[19];
         const double s = e0 * e0 + e1 * e1;
-        double rho = s, wt = 1.0;
-        if (huber > 0.0) {
-            const double r = sqrt(s);
-            if (!(s <= huber * huber)) rho = (2.0 * huber) * r - huber * huber;
-            if (!(r <= huber)) wt = huber / r;
-        }
+        double rho, wt;
+        mv::huber_loss(s, huber, rho, wt);
         part = part + rho;
         if (jac) {
 #pragma unroll
@@ -299,23 +282,17 @@ __device__ void linearize(const Prob &Q, const float *pose, const unsigned char 
             }
         }
     }
-    s_part[tid] = part;
     if (jac) {
 #pragma unroll
         for (int i = 0; i < NH; i++) Hp[i * NT + tid] = hp[i];
     }
-    __syncthreads();
-    if (tid == 0) {
-        double c = 0.0;
-        for (int i = 0; i < NT; i++) c = c + s_part[i];
-        *out = c;
-    }
-    if (jac && tid < NH) {
-        double c = 0.0;
-        for (int i = 0; i < NT; i++) c = c + Hp[tid * NT + i];
-        s_H[tid] = tid < 21 ? c : 0.0 - c;
-    }
-    __syncthreads();
+    mv::tree_sum_256(part, s_part, out, [&] {  // between the tree's barriers: the 27 sums
+        if (jac && tid < NH) {
+            double c = 0.0;
+            for (int i = 0; i < NT; i++) c = c + Hp[tid * NT + i];
+            s_H[tid] = tid < 21 ? c : 0.0 - c;
+        }
+    });
 }
 
 __global__ __launch_bounds__(NT) void k_pnp_solve(mv_pnp_params P, int batch, int cap, const int *__restrict__ nArr,
@@ -328,9 +305,10 @@ __global__ __launch_bounds__(NT) void k_pnp_solve(mv_pnp_params P, int batch, in
     __shared__ double s_part[NT], s_key[NE], s_full[MV_PNP_SURVIVORS], s_H[NH], s_L[28], s_x[6];
     __shared__ float s_hp[NE][7], s_pose[7], s_cand[7], s_prior[7];
     __shared__ int s_surv[MV_PNP_SURVIVORS], s_wc[NT / 64], s_m, s_win, s_cnt;
-    __shared__ int s_stop, s_relin, s_fail, s_acc;
-    __shared__ double s_lambda, s_cost, s_candc, s_out;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ int s_fail;
+    __shared__ mv::LmState s_lm;
+    __shared__ double s_candc, s_out;
+    const int tid = threadIdx.x;
     double *const X0 = s_dyn, *const X1 = X0 + cap, *const X2 = X1 + cap, *const U = X2 + cap, *const V = U + cap;
     int *const vidx = reinterpret_cast<int *>(V + cap);
     unsigned char *const inl = reinterpret_cast<unsigned char *>(vidx + cap);
@@ -355,11 +333,7 @@ __global__ __launch_bounds__(NT) void k_pnp_solve(mv_pnp_params P, int batch, in
                 a0 = p3[3l * i], a1 = p3[3l * i + 1], a2 = p3[3l * i + 2], b0 = p2[2l * i], b1 = p2[2l * i + 1];
                 valid = isfinite(a0) && isfinite(a1) && isfinite(a2) && isfinite(b0) && isfinite(b1);
             }
-            const unsigned long long bal = __ballot(valid);
-            if (lane == 0) s_wc[wave] = __popcll(bal);
-            __syncthreads();
-            int off = s_m + __popcll(bal & ((1ull << lane) - 1ull));
-            for (int w = 0; w < wave; w++) off += s_wc[w];
+            const int off = s_m + tr::block_rank(valid, s_wc);
             if (valid) {
                 X0[off] = a0, X1[off] = a1, X2[off] = a2, U[off] = b0, V[off] = b1;
                 vidx[off] = i;
@@ -479,14 +453,14 @@ __global__ __launch_bounds__(NT) void k_pnp_solve(mv_pnp_params P, int batch, in
                 score_all(Q, s_pose, true, inl, s_part, &s_out, &s_cnt);
                 if (s_cnt == 0) continue;  // uniform
                 if (tid == 0) {
-                    s_lambda = P.lambda_init;
-                    s_stop = 0, s_relin = 0, s_fail = 0, s_acc = 0;
+                    mv::lm_reset(s_lm, P.lambda_init);
+                    s_fail = 0;
                 }
-                linearize(Q, s_pose, inl, true, P.huber_px, s_part, Hp, s_H, &s_cost);
+                linearize(Q, s_pose, inl, true, P.huber_px, s_part, Hp, s_H, &s_lm.cost);
                 for (int it = 0; it < P.max_iters; it++) {
-                    if (s_stop) break;  // uniform: written before the last barrier
-                    if (s_relin) linearize(Q, s_pose, inl, true, P.huber_px, s_part, Hp, s_H, &s_cost);
-                    const double lam = s_lambda;
+                    if (s_lm.stop) break;  // uniform: written before the last barrier
+                    if (s_lm.relin) linearize(Q, s_pose, inl, true, P.huber_px, s_part, Hp, s_H, &s_lm.cost);
+                    const double lam = s_lm.lambda;
                     if (tid == 0) {
                         // damp; Cholesky with the right-hand side as row 6; back-substitute; retract
                         for (int i = 0; i < 28; i++) s_L[i] = s_H[i];
@@ -511,49 +485,16 @@ __global__ __launch_bounds__(NT) void k_pnp_solve(mv_pnp_params P, int batch, in
                             for (int k = i + 1; k < 6; k++) acc = acc - s_L[tri(k, i)] * s_x[k];
                             s_x[i] = acc / s_L[tri(i, i)];
                         }
-                        const double h0 = 0.5 * s_x[0], h1 = 0.5 * s_x[1], h2 = 0.5 * s_x[2];
-                        const double nn = sqrt(((1.0 + h0 * h0) + h1 * h1) + h2 * h2);
-                        const double a0 = 1.0 / nn, a1 = h0 / nn, a2 = h1 / nn, a3 = h2 / nn;
-                        const double b0 = s_pose[0], b1 = s_pose[1], b2 = s_pose[2], b3 = s_pose[3];
-                        const double t0 = s_pose[4], t1 = s_pose[5], t2 = s_pose[6];
-                        const double o0 = ((a0 * b0 - a1 * b1) - a2 * b2) - a3 * b3;
-                        const double o1 = ((a0 * b1 + a1 * b0) + a2 * b3) - a3 * b2;
-                        const double o2 = ((a0 * b2 - a1 * b3) + a2 * b0) + a3 * b1;
-                        const double o3 = ((a0 * b3 + a1 * b2) - a2 * b1) + a3 * b0;
-                        const double mm = sqrt(((o0 * o0 + o1 * o1) + o2 * o2) + o3 * o3);
-                        const double ww = a0 * a0, xx = a1 * a1, yy = a2 * a2, zz = a3 * a3;
-                        const double R0 = ((ww + xx) - yy) - zz, R1 = 2.0 * (a1 * a2 - a0 * a3),
-                                     R2 = 2.0 * (a1 * a3 + a0 * a2);
-                        const double R3 = 2.0 * (a1 * a2 + a0 * a3), R4 = ((ww - xx) + yy) - zz,
-                                     R5 = 2.0 * (a2 * a3 - a0 * a1);
-                        const double R6 = 2.0 * (a1 * a3 - a0 * a2), R7 = 2.0 * (a2 * a3 + a0 * a1),
-                                     R8 = ((ww - xx) - yy) + zz;
-                        s_cand[0] = (float)(o0 / mm);
-                        s_cand[1] = (float)(o1 / mm);
-                        s_cand[2] = (float)(o2 / mm);
-                        s_cand[3] = (float)(o3 / mm);
-                        s_cand[4] = (float)(((R0 * t0 + R1 * t1) + R2 * t2) + s_x[3]);
-                        s_cand[5] = (float)(((R3 * t0 + R4 * t1) + R5 * t2) + s_x[4]);
-                        s_cand[6] = (float)(((R6 * t0 + R7 * t1) + R8 * t2) + s_x[5]);
+                        mv::retract_pose(s_x, s_pose, s_cand);
                     }
                     __syncthreads();
                     linearize(Q, s_cand, inl, false, P.huber_px, s_part, Hp, s_H, &s_candc);
                     if (tid == 0) {
-                        const double cur = s_cost, cand = s_candc;
-                        if (!s_fail && isfinite(cand) && cand < cur) {
-                            if (cur - cand < P.rel_tol * cur) s_stop = 1;
-                            s_cost = cand;
-                            s_lambda = dmax(lam * P.lambda_down, P.lambda_min);
-                            s_relin = 1, s_acc = 1;
-                        } else {
-                            s_lambda = lam * P.lambda_up;
-                            if (s_lambda > P.lambda_max) s_stop = 1;
-                            s_relin = 0, s_acc = 0;
-                        }
+                        mv::lm_decide(P, s_lm, s_fail != 0, s_candc);
                         s_fail = 0;
                     }
                     __syncthreads();
-                    if (s_acc && tid < 7) s_pose[tid] = s_cand[tid];
+                    if (s_lm.acc && tid < 7) s_pose[tid] = s_cand[tid];
                     __syncthreads();
                 }
                 __syncthreads();
@@ -585,7 +526,7 @@ __global__ __launch_bounds__(NT) void k_pnp_gather(int cap, int track_cap, const
                                                    const float *__restrict__ kp_new, float *__restrict__ pts3,
                                                    float *__restrict__ pts2, int *__restrict__ count) {
     __shared__ int s_wc[NT / 64], s_m;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const size_t s = blockIdx.x;
     const int np = min(max(n_prev[s], 0), cap), nn = min(max(n_new[s], 0), cap);
     const int *tr = track_id + s * tid_stride, *mi = match_idx + s * cap, *fl = flags + s * track_cap;
@@ -602,11 +543,7 @@ __global__ __launch_bounds__(NT) void k_pnp_gather(int cap, int track_cap, const
             valid = j >= 0 && j < nn && t >= 0 && t < track_cap;
             if (valid) valid = fl[t] == 0;
         }
-        const unsigned long long bal = __ballot(valid);
-        if (lane == 0) s_wc[wave] = __popcll(bal);
-        __syncthreads();
-        int off = s_m + __popcll(bal & ((1ull << lane) - 1ull));
-        for (int w = 0; w < wave; w++) off += s_wc[w];
+        const int off = s_m + tr::block_rank(valid, s_wc);
         if (valid) {
             o3[3l * off] = L[3l * t], o3[3l * off + 1] = L[3l * t + 1], o3[3l * off + 2] = L[3l * t + 2];
             o2[2l * off] = kp[2l * j], o2[2l * off + 1] = kp[2l * j + 1];
@@ -623,26 +560,17 @@ __global__ __launch_bounds__(NT) void k_pnp_gather(int cap, int track_cap, const
     if (tid == 0) count[s] = c;
 }
 
-bool in_range(double v, double lo, double hi) { return isfinite(v) && v >= lo && v <= hi; }
-
 }  // namespace
 
 extern "C" void mv_pnp_params_default(mv_pnp_params *p) {
     if (!p) return;
+    mv::lm_params_default(p);
     p->hypotheses = 256;
     p->refine_rounds = 2;
     p->min_inliers = 6;
-    p->max_iters = 10;
     p->seed = 0x9E3779B97F4A7C15ull;
     p->inlier_thresh_px = 2.0;
     p->min_depth = 0.1;
-    p->lambda_init = 1e-4;
-    p->lambda_up = 10.0;
-    p->lambda_down = 0.1;
-    p->lambda_min = 1e-10;
-    p->lambda_max = 1e10;
-    p->diag_floor = 1e-6;
-    p->rel_tol = 1e-6;
     p->huber_px = 0.0;
 }
 
@@ -666,23 +594,13 @@ extern "C" int mv_pnp_solve_dev(mv_context *ctx, const mv_pnp_params *p, int bat
     MV_REQUIRE(ctx && p && batch > 0 && cap >= 1 && cap <= MV_PNP_MAX_CAP);
     MV_REQUIRE(n && pts3 && pts2 && cameras && pose_out && inlier && num_inliers && best_hyp && status && cost);
     MV_REQUIRE(p->hypotheses >= 1 && p->hypotheses <= MV_PNP_MAX_HYPOTHESES);
-    MV_REQUIRE(p->refine_rounds >= 0 && p->refine_rounds <= 16 && p->max_iters >= 0 && p->max_iters <= 1000);
-    MV_REQUIRE(p->min_inliers >= 0);
-    const double big = 1e300;
-    MV_REQUIRE(in_range(p->inlier_thresh_px, 0.0, big) && in_range(p->min_depth, 0.0, big));
-    MV_REQUIRE(in_range(p->lambda_init, 0.0, big) && p->lambda_init > 0.0);
-    MV_REQUIRE(in_range(p->lambda_up, 1.0, big) && in_range(p->lambda_down, 0.0, 1.0) && p->lambda_down > 0.0);
-    MV_REQUIRE(in_range(p->lambda_min, 0.0, big) && in_range(p->lambda_max, p->lambda_min, big));
-    MV_REQUIRE(in_range(p->diag_floor, 0.0, big) && in_range(p->rel_tol, 0.0, big) && in_range(p->huber_px, 0.0, big));
+    MV_REQUIRE(p->refine_rounds >= 0 && p->refine_rounds <= 16 && p->min_inliers >= 0);
+    MV_REQUIRE(mv::in_range(p->inlier_thresh_px, 0.0, 1e300) && mv::in_range(p->min_depth, 0.0, 1e300));
+    MV_REQUIRE(mv::lm_params_ok(*p, p->huber_px));
     MV_REQUIRE((long)batch * cap < (1l << 31));
     MV_HIP_TRY(hipSetDevice(ctx->device));
-    // two workgroups per CU (the problems queue on the workgroups there are); MV_PNP_GRID (tests):
-    // another workgroup count -- more problems than workgroups, slabs reused
-    int grid = (int)std::min<long>(batch, 2l * std::max(ctx->cu_count, 1));
-    if (const char *e = getenv("MV_PNP_GRID")) {
-        const int g = atoi(e);
-        if (g > 0) grid = std::min(batch, g);
-    }
+    // 54 KiB of Hp a workgroup: two workgroups per CU stay far below the scratch cap
+    const int grid = mv::solver_grid(ctx, batch, mv::carve_bytes(pnp_scratch_layout, (size_t)1), "MV_PNP_GRID");
     PnpScratch m;
     if (!mv::carve(mv::scratch, ctx, [&](mv::Carve &c) { m = pnp_scratch_layout(c, (size_t)grid); }))
         return MV_ERR_OUT_OF_MEMORY;

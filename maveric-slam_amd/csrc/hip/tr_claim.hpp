@@ -1,7 +1,10 @@
-// tr_claim.hpp -- the column claim of feature_tracks.h step 1, shared by k_tracks.hip (k_tr_claim)
-// and k_mapupd.hip (k_mu_extend): a proposer's 64-bit key holds (score, row) completely, so one
-// atomicMax per proposer over the column's key decides the winner under any schedule, and the
-// rank of a flagged thread within its workgroup.
+// tr_claim.hpp -- the column claim of feature_tracks.h step 1: a proposer's 64-bit key holds
+// (score, row) completely, so one atomicMax per proposer over the column's key decides the winner
+// under any schedule.  Users: k_tracks.hip (k_tr_claim), k_mapupd.hip (k_mu_extend) and k_map.hip
+// (k_map_match: a keypoint accepts one landmark).
+// And block_rank, the rank of a flagged thread within its workgroup: the ballot compaction in
+// ascending order of k_tracks.hip, k_mapupd.hip, k_bawin.hip, k_pnp.hip (k_pnp_gather and
+// k_pnp_solve's staging) and k_map.hip (the emitted pairs); clampn for a count read from memory.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -37,7 +40,9 @@ __device__ __forceinline__ bool claim_propose(unsigned long long *keys, int i, i
     return true;
 }
 
-// rank of this thread among the threads of the block with `flag`; s_wave [waves of the block]
+// rank of this thread among the threads of the block with `flag`; s_wave [waves of the block] (LDS)
+// keeps every wave's count: their sum is the block's total.  One barrier, after the counts are
+// written; the caller puts one before s_wave is written again.
 __device__ __forceinline__ int block_rank(bool flag, int *s_wave) {
     const unsigned long long m = __ballot(flag);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;

@@ -9,6 +9,7 @@
 #include <math.h>
 
 #include "feature_tracks.h"
+#include "mv_lm.hpp"
 
 namespace tr {
 
@@ -27,20 +28,6 @@ __device__ __forceinline__ void load_obs(Obs &o, const float *__restrict__ pose,
     o.v = (double)p.y;
 }
 
-__device__ __forceinline__ void rot(const double *q, double *R) {
-    const double w = q[0], x = q[1], y = q[2], z = q[3];
-    const double ww = w * w, xx = x * x, yy = y * y, zz = z * z;
-    R[0] = ((ww + xx) - yy) - zz;
-    R[1] = 2.0 * (x * y - w * z);
-    R[2] = 2.0 * (x * z + w * y);
-    R[3] = 2.0 * (x * y + w * z);
-    R[4] = ((ww - xx) + yy) - zz;
-    R[5] = 2.0 * (y * z - w * x);
-    R[6] = 2.0 * (x * z - w * y);
-    R[7] = 2.0 * (y * z + w * x);
-    R[8] = ((ww - xx) - yy) + zz;
-}
-
 struct Midpoint {
     double A00 = 0.0, A01 = 0.0, A02 = 0.0, A11 = 0.0, A12 = 0.0, A22 = 0.0, b0 = 0.0, b1 = 0.0, b2 = 0.0;
     double c00 = 0.0, c01 = 0.0, c02 = 0.0, e00 = 0.0, e01 = 0.0, e02 = 0.0;
@@ -50,7 +37,7 @@ struct Midpoint {
     // one observation into the normal equations; `first`: the track's first observation
     __device__ __forceinline__ void add(const Obs &cur, bool first) {
         double R[9];
-        rot(cur.q, R);
+        mv::quat_rot(cur.q, R);
         const double r0 = (cur.u - cur.k[2]) / cur.k[0], r1 = (cur.v - cur.k[3]) / cur.k[1];
         const double e0 = (R[0] * r0 + R[3] * r1) + R[6];
         const double e1 = (R[1] * r0 + R[4] * r1) + R[7];
@@ -101,7 +88,7 @@ struct Midpoint {
     __device__ __forceinline__ int check(const Obs &cur, double min_depth, double mr2) const {
         int flags = 0;
         double R[9];
-        rot(cur.q, R);
+        mv::quat_rot(cur.q, R);
         const double p0 = ((R[0] * X0 + R[1] * X1) + R[2] * X2) + cur.q[4];
         const double p1 = ((R[3] * X0 + R[4] * X1) + R[5] * X2) + cur.q[5];
         const double p2 = ((R[6] * X0 + R[7] * X1) + R[8] * X2) + cur.q[6];

@@ -271,13 +271,18 @@ def _np(a):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
-def kp_params(**kw):
-    """mv_kp_params (conf_thresh 0.015, nms_dist 4, border 4 -- pairwise_pnp.py:589-591, :99)."""
-    p = KpParams()
-    lib().mv_kp_params_default(ctypes.byref(p))
+def _params(cls, default_fn_name, kw):
+    """A params struct of `cls` filled by the library's `default_fn_name`, then the overrides in kw."""
+    p = cls()
+    getattr(lib(), default_fn_name)(ctypes.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     return p
+
+
+def kp_params(**kw):
+    """mv_kp_params (conf_thresh 0.015, nms_dist 4, border 4 -- pairwise_pnp.py:589-591, :99)."""
+    return _params(KpParams, "mv_kp_params_default", kw)
 
 
 # ---------------- trajectory (include/trajectory.h; python/compute_trajectory.py) ----------------
@@ -480,60 +485,36 @@ def track_params(semantics=AS_BUILT):
 
 def landmark_params(**kw):
     """mv_landmark_params (cos_min_parallax cos(1 degree), min_depth 0.1, max_reproj_px 2)."""
-    p = LandmarkParams()
-    lib().mv_landmark_params_default(ctypes.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _params(LandmarkParams, "mv_landmark_params_default", kw)
 
 
 def ba_params(**kw):
     """mv_ba_params with its defaults (max_iters 10, lambda_init 1e-4, up 10, down 0.1, min 1e-10,
     max 1e10, diag_floor 1e-6, rel_tol 1e-6, huber_px 0)."""
-    p = BaParams()
-    lib().mv_ba_params_default(ctypes.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _params(BaParams, "mv_ba_params_default", kw)
 
 
 def pg_params(**kw):
     """mv_pg_params with its defaults (max_iters 10, lambda_init 1e-4, up 10, down 0.1, min 1e-10,
     max 1e10, diag_floor 1e-6, rel_tol 1e-6, huber 0)."""
-    p = PgParams()
-    lib().mv_pg_params_default(ctypes.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _params(PgParams, "mv_pg_params_default", kw)
 
 
 def pnp_params(**kw):
     """mv_pnp_params with its defaults (hypotheses 256, refine_rounds 2, min_inliers 6, max_iters 10,
     inlier_thresh_px 2, min_depth 0.1 and mv_ba_params' LM fields)."""
-    p = PnpParams()
-    lib().mv_pnp_params_default(ctypes.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _params(PnpParams, "mv_pnp_params_default", kw)
 
 
 def map_params(**kw):
     """mv_map_params with its defaults (radius_px 16, min_depth 0.1, thresh 0.8, ratio 0 = off, and
     the width / height binning hint)."""
-    p = MapParams()
-    lib().mv_map_params_default(ctypes.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _params(MapParams, "mv_map_params_default", kw)
 
 
 def ba_window_params(**kw):
     """mv_ba_window_params with its defaults (min_shared 15, n_fixed 2, min_obs 2)."""
-    p = BaWindowParams()
-    lib().mv_ba_window_params_default(ctypes.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _params(BaWindowParams, "mv_ba_window_params_default", kw)
 
 
 def pg_envelope(nodes, edge_i, edge_j, node_fixed=None):
