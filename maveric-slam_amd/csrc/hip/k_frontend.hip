@@ -149,36 +149,6 @@ __global__ __launch_bounds__(256) void k_softmax(int total_rows, int cells, cons
     }
 }
 
-// ---------------------------------------------------------------------------
-// Block-wide exclusive scan helper (1024 threads = 16 waves).
-// ---------------------------------------------------------------------------
-template <int NT>
-__device__ __forceinline__ int block_exclusive_scan(int v, int *total, int *wsum) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        int y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) wsum[w] = x;
-    __syncthreads();
-    if (w == 0) {
-        int s = lane < NT / 64 ? wsum[lane] : 0;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            int y = __shfl_up(s, o, 64);
-            if (lane >= o) s += y;
-        }
-        if (lane < NT / 64) wsum[lane] = s;  // inclusive wave prefix
-    }
-    __syncthreads();
-    int off = (w > 0 ? wsum[w - 1] : 0) + x - v;
-    *total = wsum[NT / 64 - 1];
-    __syncthreads();
-    return off;
-}
-
 // k_top_n_select: ONE WAVE per frame (4 frames per 256-thread block, no block barrier): the frame's
 // cells in chunks of 64 consecutive ones (coalesced loads), a ballot of the valid cells per chunk
 // -- so the selection keeps patch order by construction: a selected cell's slot is the running
@@ -286,11 +256,7 @@ struct QueryResult {  // one per (pair, query slot), consumed by k_window_compac
 
 __device__ __forceinline__ int wrap_mul(int a, int b) { return (int)((unsigned)a * (unsigned)b); }
 
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
+using wave::wave_sum;
 
 // strict "a better than b" for as-intended (dot^2/na) with tie -> lower order
 __device__ __forceinline__ bool exact_better(long long da, long long na, int ka, long long db, long long nb,
@@ -1211,7 +1177,7 @@ __global__ __launch_bounds__(1024) void k_window_compact(int N, int rows, int ma
     int cnt = 0;
     for (int q = q0; q < q1; q++) cnt += (q < nsel && r[q].found) ? 1 : 0;
     int total;
-    int k = block_exclusive_scan<1024>(cnt, &total, wsum);
+    int k = wave::block_scan_excl<1024>(cnt, &total, wsum);
     for (int q = q0; q < q1; q++) {
         if (!(q < nsel && r[q].found)) continue;
         if (k < max_matches) {

@@ -8,11 +8,14 @@
 // As-intended (k_pose_ransac in k_pose_intended.hip): normalised 8-point
 // hypotheses, Sampson scoring, cheirality, Gauss-Newton refinement.
 #include "mv_internal.hpp"
+#include "mv_pair.hpp"
 #include "mv_svd3.hpp"
+#include "mv_wave.hpp"
 
 namespace {
 
 using mv::Mat3;
+using wave::block_scan_excl;
 
 // pnp_solver.c:89-105, evaluated exactly as the reference does
 __device__ __forceinline__ float reproj_error(float x1, float y1, float x2, float y2, const Mat3 &E) {
@@ -62,35 +65,8 @@ __global__ void k_recover_pose(const float *E, float *R1, float *R2, float *t) {
     for (int i = 0; i < 3; i++) t[i] = tt[i];
 }
 
-// Block-ordered compaction of an inlier list (order = point index), cap 1000.
-template <int NT>
-__device__ __forceinline__ int block_scan_excl(int v, int *total, int *wsum) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        int y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) wsum[w] = x;
-    __syncthreads();
-    if (w == 0) {
-        int s = lane < NT / 64 ? wsum[lane] : 0;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            int y = __shfl_up(s, o, 64);
-            if (lane >= o) s += y;
-        }
-        if (lane < NT / 64) wsum[lane] = s;
-    }
-    __syncthreads();
-    const int off = (w > 0 ? wsum[w - 1] : 0) + x - v;
-    *total = wsum[NT / 64 - 1];
-    __syncthreads();
-    return off;
-}
-
-// single pair stub RANSAC (one 256-thread block), pts as [n][2]
+// single pair stub RANSAC (one 256-thread block), pts as [n][2]: block-ordered compaction of the
+// inlier list (order = point index), cap 1000
 __global__ __launch_bounds__(256) void k_ransac_stub(int n, const float *__restrict__ p1,
                                                      const float *__restrict__ p2, float thr,
                                                      float *__restrict__ E_out, int *__restrict__ inliers,
@@ -135,16 +111,8 @@ __global__ __launch_bounds__(256) void k_pose_as_built(int cap, const int *__res
     const int i0 = threadIdx.x * per, i1 = min(i0 + per, n);
     int cnt = 0, nm = 0;
     for (int i = i0; i < i1; i++) {
-        float x1 = pts0[((size_t)b * cap + i) * 2], y1 = pts0[((size_t)b * cap + i) * 2 + 1], x2, y2;
-        if (match_idx) {
-            const int j = match_idx[(size_t)b * cap + i];
-            if ((unsigned)j >= (unsigned)cap) continue;  // -1 or out of range: no match
-            x2 = kp1[((size_t)b * cap + j) * 2];
-            y2 = kp1[((size_t)b * cap + j) * 2 + 1];
-        } else {
-            x2 = pts1[((size_t)b * cap + i) * 2];
-            y2 = pts1[((size_t)b * cap + i) * 2 + 1];
-        }
+        float x1, y1, x2, y2;
+        if (!mv::load_pair(b, cap, i, pts0, pts1, match_idx, kp1, x1, y1, x2, y2)) continue;  // no match
         nm++;
         if (reproj_error(x1, y1, x2, y2, E) < thr) cnt++;
     }
@@ -170,16 +138,9 @@ __global__ __launch_bounds__(256) void k_pose_as_built(int cap, const int *__res
 
 namespace mv {
 
-int launch_intended_pose(hipStream_t s, void *scratch, const mv_pose_params *p, int batch, int cap, const int *n,
-                         const float *pts0, const float *pts1, const int *match_idx, const float *kp1, float *T,
-                         int *num_matches, int *num_inliers, int *status);
-size_t intended_pose_scratch_bytes(int batch, int cap);
-
-size_t pose_scratch_bytes(int batch, int cap) { return intended_pose_scratch_bytes(batch, cap); }
-
-int launch_pose(hipStream_t s, void *scratch, const mv_pose_params *p, int batch, int cap, const int *n,
-                const float *pts0, const float *pts1, const int *match_idx, const float *kp1, float *T,
-                int *num_matches, int *num_inliers, int *status) {
+int launch_pose(hipStream_t s, const mv_pose_params *p, int batch, int cap, const int *n, const float *pts0,
+                const float *pts1, const int *match_idx, const float *kp1, float *T, int *num_matches,
+                int *num_inliers, int *status) {
     MV_REQUIRE(p && batch > 0 && cap > 0 && n && pts0 && T && num_inliers && status);
     MV_REQUIRE(match_idx ? kp1 != nullptr : pts1 != nullptr);
     if (p->semantics == MV_AS_BUILT) {
@@ -187,8 +148,8 @@ int launch_pose(hipStream_t s, void *scratch, const mv_pose_params *p, int batch
                   p->inlier_thresh, T, num_matches, num_inliers, status);
         return MV_OK;
     }
-    return launch_intended_pose(s, scratch, p, batch, cap, n, pts0, pts1, match_idx, kp1, T, num_matches,
-                                num_inliers, status);
+    return launch_intended_pose(s, p, batch, cap, n, pts0, pts1, match_idx, kp1, T, num_matches, num_inliers,
+                                status);
 }
 
 int launch_ransac_stub(hipStream_t s, int n, const float *pts1, const float *pts2, float thresh, float *E,

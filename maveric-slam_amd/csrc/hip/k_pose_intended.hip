@@ -9,7 +9,7 @@
 //      (pnp_solver.c:42-50), and takes its null vector from a Householder QR
 //      of A^T (backward stable, no pivoting, static register indexing);
 //      hypotheses are MSAC-scored (sum of min(Sampson^2, (thr_px / f)^2)) on an evenly
-//      strided subset of 128 correspondences (LDS broadcast reads);
+//      strided subset of PE_PREM correspondences (LDS broadcast reads);
 //   3. preemption: the 2 best of each wave survive and are MSAC-scored on ALL
 //      correspondences by the whole block; the two lowest (cost, hypothesis id) are the
 //      starts of the refinement;
@@ -27,11 +27,14 @@
 //   6. the refined pose with the lower robust cost (Cauchy at thr, capped at 3 thr) wins;
 //      the second start is refined only when the first did not reach an exact fit.
 // Output T = [R | t] with x1 ~ R x0 + t, |t| = 1 (the OpenCV recoverPose convention).
+//
+// One function per phase, called in this order by k_pose_ransac; DESIGN 4.3 has the table and what a
+// change to one of them has to re-check.
 #include <math.h>
 
-#include <type_traits>
-
 #include "mv_internal.hpp"
+#include "mv_pair.hpp"
+#include "mv_wave.hpp"
 
 // This kernel is the as-INTENDED pose, checked against ground truth within a tolerance,
 // not bit-exact against the oracle: let every a * b + c contract to one FMA here (the
@@ -41,30 +44,17 @@
 
 namespace {
 
+using wave::wave_sum;
+
 constexpr int NT = 256;
-// correspondences in the preemptive scoring subset of the 256 hypotheses (the 8 survivors are then
-// scored on all).  Same-box A/B (profiles/r05u_pose_prem_ab.log): 128 / 64 / 32 points -- exact
-// data 0.498 / 0.442 / 0.415 ms, 0.5 px + 20 % outliers 0.996 / 0.939 / 0.905 ms per 8192 pairs,
-// pose errors unchanged (realistic line p99: rotation 0.085 / 0.086 / 0.086 deg, translation
-// direction 2.51 / 2.54 / 2.56 deg), every pose test green; 64 kept (the subset still ranks
-// hypotheses under heavier contamination than the bench's)
+// correspondences in the preemptive scoring subset of the 256 hypotheses: 64 still ranks hypotheses
+// under heavier contamination than the bench's, 32 was 6 % faster (profiles/r05u_pose_prem_ab.log)
 constexpr int PE_PREM = 64;
-// waves per SIMD, a lower bound.  Built without SLP packing (Makefile, profiles/r05al_pose_noslp_ab.log)
-// the kernel takes 119 VGPRs and no scratch, i.e. 4 waves per SIMD either way; the history below is
-// that of the SLP-packed build, whose cross-stream nondeterminism went with the packing.
-// SLP-packed: 3: 155 VGPRs, no scratch.  4 (128 VGPRs, 38 VGPRs + 22 SGPRs spilled, 96 B of
-// scratch per lane) was faster (0.523 vs 0.564 ms exact, 1.07 vs 1.17 ms noisy,
-// profiles/r04y_pose_waves_ab.log) but NOT deterministic: with the image -> pose chain running on
-// three streams at once, some poses of a 256-pair track came out different from the same track
-// run alone (matches identical; tools/dbg_pipelines.py, profiles/r05m_pose_determinism.log), the
-// spill-free build bit-identical in every round -- so no scratch in this kernel.  (Measured and
-// not kept: every wave solving its group's normal equations itself, one barrier per Gauss-Newton
-// iteration instead of two: 1.105 vs 1.097-1.113 ms noisy, profiles/r05p_pose_rsolve_ab.log; each
-// start refined by ONE wave with wave reductions and no block barrier at all: 1.046-1.050 vs
-// 0.995-0.996 ms noisy, 0.516-0.517 vs 0.494 exact -- the per-point passes, not the barriers, set
-// the pace -- profiles/r05r_pose_wavegn_ab.log.)
+// waves per SIMD, a lower bound: built without SLP packing the kernel takes 119 VGPRs and no scratch,
+// 4 waves per SIMD either way; no scratch, ever (DESIGN A.5, profiles/r05al_pose_noslp_ab.log)
 constexpr int PE_WAVES = 3;
 constexpr int MAXP = 4096;  // correspondences per pair held in LDS (float4 each)
+constexpr int SURV = 2, NS = 4 * SURV;  // survivors of the preemption per wave, per block
 
 __device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
     x += 0x9E3779B97F4A7C15ull;
@@ -134,29 +124,51 @@ __device__ __forceinline__ bool eight_point(const float4 *P, const int idx[8], f
     return true;
 }
 
+// ---- Sampson distance of (x1, y1) <-> (x2, y2) under E = e[9]: num^2 / den ----
+// affine2: a x + b y + c.  The ASSOCIATION is the caller's and deliberate: under fp contract(fast)
+// it decides which products fuse, so the two forms round differently -- the scalar scoring adds
+// left to right, the packed scoring adds a x + (b y + c) = fma(a, x, fma(b, y, c)), two chained
+// v_pk_fma_f32.  The packed form spells its FMAs out to fix their operand ORDER, a splat factor
+// first: a splat of a register pair's high half (p.y, p.w of a float4) is then an op_sel on src0
+// -- on src1 it is the form the hardware misreads (Makefile, tests/test_isa_guard.py), and the
+// compiler orders the factors of a contracted a * x as it likes.
+template <bool RIGHT, typename A, typename X, typename C>
+__device__ __forceinline__ auto affine2(A a, X x, A b, X y, C c) {
+    if constexpr (RIGHT) {
+        using T = decltype(a * x);
+        if constexpr (sizeof(X) < sizeof(A))  // x, y are the splats
+            return __builtin_elementwise_fma((T)x, (T)a, __builtin_elementwise_fma((T)y, (T)b, (T)c));
+        else
+            return __builtin_elementwise_fma((T)a, (T)x, __builtin_elementwise_fma((T)b, (T)y, (T)c));
+    } else {
+        return a * x + b * y + c;
+    }
+}
+// Operands float or packed f2v (two points under one hypothesis: X packed; one point under two
+// hypotheses: E packed); num and den take the type of their product.
+typedef float f2v __attribute__((ext_vector_type(2)));
+template <bool RIGHT, typename E, typename X, typename T>
+__device__ __forceinline__ void sampson_terms(const E *e, X x1, X y1, X x2, X y2, T &num, T &den) {
+    const T ex0 = affine2<RIGHT>(e[0], x1, e[1], y1, e[2]);
+    const T ex1 = affine2<RIGHT>(e[3], x1, e[4], y1, e[5]);
+    const T ex2 = affine2<RIGHT>(e[6], x1, e[7], y1, e[8]);
+    const T etx0 = affine2<RIGHT>(e[0], x2, e[3], y2, e[6]);
+    const T etx1 = affine2<RIGHT>(e[1], x2, e[4], y2, e[7]);
+    num = affine2<RIGHT>(x2, ex0, y2, ex1, ex2);
+    den = ex0 * ex0 + ex1 * ex1 + etx0 * etx0 + etx1 * etx1;
+}
+
 __device__ __forceinline__ bool sampson_inlier(const float e[9], float4 p, float thr2) {
-    const float x1 = p.x, y1 = p.y, x2 = p.z, y2 = p.w;
-    const float ex0 = e[0] * x1 + e[1] * y1 + e[2];
-    const float ex1 = e[3] * x1 + e[4] * y1 + e[5];
-    const float ex2 = e[6] * x1 + e[7] * y1 + e[8];
-    const float etx0 = e[0] * x2 + e[3] * y2 + e[6];
-    const float etx1 = e[1] * x2 + e[4] * y2 + e[7];
-    const float num = x2 * ex0 + y2 * ex1 + ex2;
-    const float den = ex0 * ex0 + ex1 * ex1 + etx0 * etx0 + etx1 * etx1;
+    float num, den;
+    sampson_terms<false>(e, p.x, p.y, p.z, p.w, num, den);
     return num * num < thr2 * den;
 }
 
 // MSAC cost of one correspondence: min(Sampson^2, thr^2) (fast reciprocal: the
 // cost only has to be deterministic, not correctly rounded)
 __device__ __forceinline__ float msac_cost(const float e[9], float4 p, float thr2, int &inl) {
-    const float x1 = p.x, y1 = p.y, x2 = p.z, y2 = p.w;
-    const float ex0 = e[0] * x1 + e[1] * y1 + e[2];
-    const float ex1 = e[3] * x1 + e[4] * y1 + e[5];
-    const float ex2 = e[6] * x1 + e[7] * y1 + e[8];
-    const float etx0 = e[0] * x2 + e[3] * y2 + e[6];
-    const float etx1 = e[1] * x2 + e[4] * y2 + e[7];
-    const float num = x2 * ex0 + y2 * ex1 + ex2;
-    const float den = ex0 * ex0 + ex1 * ex1 + etx0 * etx0 + etx1 * etx1;
+    float num, den;
+    sampson_terms<false>(e, p.x, p.y, p.z, p.w, num, den);
     const bool in = num * num < thr2 * den;
     inl += in ? 1 : 0;
     return in ? num * num * __builtin_amdgcn_rcpf(den) : thr2;
@@ -165,16 +177,10 @@ __device__ __forceinline__ float msac_cost(const float e[9], float4 p, float thr
 // msac_cost of two correspondences at once on packed FP32 (v_pk_fma_f32 with the
 // hypothesis' coefficients splat): A = {x1 x1' y1 y1'}, B = {x2 x2' y2 y2'}, the
 // scoring subset's point-pair layout, so the operands need no register shuffling
-typedef float f2v __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f2v msac_cost2(const float e[9], float4 A, float4 B, float thr2) {
     const f2v x1 = {A.x, A.y}, y1 = {A.z, A.w}, x2 = {B.x, B.y}, y2 = {B.z, B.w};
-    const f2v ex0 = e[0] * x1 + (e[1] * y1 + e[2]);
-    const f2v ex1 = e[3] * x1 + (e[4] * y1 + e[5]);
-    const f2v ex2 = e[6] * x1 + (e[7] * y1 + e[8]);
-    const f2v etx0 = e[0] * x2 + (e[3] * y2 + e[6]);
-    const f2v etx1 = e[1] * x2 + (e[4] * y2 + e[7]);
-    const f2v num = x2 * ex0 + (y2 * ex1 + ex2);
-    const f2v den = ex0 * ex0 + ex1 * ex1 + etx0 * etx0 + etx1 * etx1;
+    f2v num, den;
+    sampson_terms<true>(e, x1, y1, x2, y2, num, den);
     const f2v nn = num * num, td = thr2 * den;
     f2v r;
     r.x = nn.x < td.x ? nn.x * __builtin_amdgcn_rcpf(den.x) : thr2;
@@ -185,14 +191,8 @@ __device__ __forceinline__ f2v msac_cost2(const float e[9], float4 A, float4 B, 
 // msac_cost of one correspondence under two hypotheses at once (packed FP32, the point's
 // coordinates splat): the survivors' full re-score
 __device__ __forceinline__ f2v msac_cost2h(const f2v E[9], float4 p, float thr2, int &na, int &nb) {
-    const float x1 = p.x, y1 = p.y, x2 = p.z, y2 = p.w;
-    const f2v ex0 = E[0] * x1 + (E[1] * y1 + E[2]);
-    const f2v ex1 = E[3] * x1 + (E[4] * y1 + E[5]);
-    const f2v ex2 = E[6] * x1 + (E[7] * y1 + E[8]);
-    const f2v etx0 = E[0] * x2 + (E[3] * y2 + E[6]);
-    const f2v etx1 = E[1] * x2 + (E[4] * y2 + E[7]);
-    const f2v num = x2 * ex0 + (y2 * ex1 + ex2);
-    const f2v den = ex0 * ex0 + ex1 * ex1 + etx0 * etx0 + etx1 * etx1;
+    f2v num, den;
+    sampson_terms<true>(E, p.x, p.y, p.z, p.w, num, den);
     const f2v nn = num * num, td = thr2 * den;
     const bool ia = nn.x < td.x, ib = nn.y < td.y;
     na += ia ? 1 : 0;
@@ -201,6 +201,25 @@ __device__ __forceinline__ f2v msac_cost2h(const f2v E[9], float4 p, float thr2,
     r.x = ia ? nn.x * __builtin_amdgcn_rcpf(den.x) : thr2;
     r.y = ib ? nn.y * __builtin_amdgcn_rcpf(den.y) : thr2;
     return r;
+}
+
+// The pose form of the same distance, for p = (x1, y1, x2, y2) under (R, t): q = R x1,
+// x2t = x2 x t, e = x2^T [t]x R x1 = x2t . q, s2 = (E x1)_{0,1}^2 + (E^T x2)_{0,1}^2 with
+// E^T x2 = R^T x2t; the Sampson distance is e / sqrt(s2).
+__device__ __forceinline__ void pose_sampson(const float (&R)[9], const float (&tv)[3], float4 p, float (&q)[3],
+                                             float (&x2t)[3], float &e, float &s2) {
+    q[0] = R[0] * p.x + R[1] * p.y + R[2];
+    q[1] = R[3] * p.x + R[4] * p.y + R[5];
+    q[2] = R[6] * p.x + R[7] * p.y + R[8];
+    x2t[0] = p.w * tv[2] - tv[1];
+    x2t[1] = tv[0] - p.z * tv[2];
+    x2t[2] = p.z * tv[1] - p.w * tv[0];
+    e = x2t[0] * q[0] + x2t[1] * q[1] + x2t[2] * q[2];
+    const float Ex1[2] = {tv[1] * q[2] - tv[2] * q[1], tv[2] * q[0] - tv[0] * q[2]};
+    float Etx2[2];
+#pragma unroll
+    for (int c = 0; c < 2; c++) Etx2[c] = R[c] * x2t[0] + R[3 + c] * x2t[1] + R[6 + c] * x2t[2];
+    s2 = Ex1[0] * Ex1[0] + Ex1[1] * Ex1[1] + Etx2[0] * Etx2[0] + Etx2[1] * Etx2[1];
 }
 
 // ---- small 3-vector algebra ----
@@ -394,25 +413,73 @@ struct PoseArgs {
     unsigned long long seed;
 };
 
-__global__ __launch_bounds__(NT, PE_WAVES) void k_pose_ransac(PoseArgs a, const int *__restrict__ nv,
-                                                    const float *__restrict__ pts0,
-                                                    const float *__restrict__ pts1,
-                                                    const int *__restrict__ match_idx,
-                                                    const float *__restrict__ kp1, float *__restrict__ T,
-                                                    int *__restrict__ num_matches, int *__restrict__ num_inliers,
-                                                    int *__restrict__ status) {
-    extern __shared__ __attribute__((aligned(16))) float4 P[];  // [min(cap, MAXP)]
-    __shared__ int wsum[4];
-    const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
-    const int n_in = min(max(nv[b], 0), a.cap);
+// The kernel's static LDS: what more than one phase touches, and the phases' hand-overs.
+struct PoseLds {
+    float4 sub[PE_PREM / 2][2];  // the scoring subset in point-pair layout (points 2k, 2k+1 in sub[k])
+    int wsum[4];                 // the gather's wave totals
+    int sh[NS];                  // survivor hypothesis ids (-1: none)
+    float sE[NS][9];             // survivor E
+    float red2[4][2 * NS];       // [wave]: the survivors' full costs, then their inlier counts
+    float E[2][9];               // the starts
+    int nh;                      // starts found (0, 1, 2)
+    bool exact;                  // the best survivor's inliers fit (almost) exactly
+    float cand[2][4][12];        // [group][candidate]: R (9), t (3)
+    float uv[2][2][3][3];        // [group]: U, V
+    int votes[4][4];             // [wave][candidate]
+    float red[2][4][22];         // [iteration parity][wave]: the Gauss-Newton sums
+    float state[2][2][16];       // [iteration parity][group]
+    float fin[4];                // [wave]: robust cost of the refined pose
+    int fin_n[4];                // [wave]: its inliers
+};
+static_assert(sizeof(PoseLds) == 3280, "the static LDS of k_pose_ransac");
 
-    // ---- 1. compaction (query order) + normalisation ----
+// The outputs of pair b: thread t < 12 writes entry t of T (v: its value), thread 0 the rest
+struct PoseOut {
+    float *T;
+    int *num_matches, *num_inliers, *status;
+    __device__ __forceinline__ void write(int b, float v, int n_all, int inliers, int st) const {
+        const int t = threadIdx.x;
+        if (t < 12) T[(size_t)b * 12 + t] = v;
+        if (t == 0) {
+            num_inliers[b] = inliers;
+            if (num_matches) num_matches[b] = n_all;
+            status[b] = st;
+        }
+    }
+    // no pose: identity, zero inliers, the status
+    __device__ __forceinline__ void write_none(int b, int n_all, int st) const {
+        const int t = threadIdx.x;
+        write(b, (t % 4 == t / 4) ? 1.f : 0.f, n_all, 0, st);
+    }
+};
+
+// Exclusive scan of v over the 256 threads, *total = the block sum.  Not wave::block_scan_excl: ONE
+// barrier (each thread sums the four wave totals itself; wsum stays valid), where that takes three.
+__device__ __forceinline__ int scan_excl_256_one_barrier(int v, int *total, int *wsum) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int x = wave::wave_scan_incl(v);
+    if (lane == 63) wsum[w] = x;
+    __syncthreads();
+    int off = x - v;
+    for (int k = 0; k < w; k++) off += wsum[k];
+    *total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    return off;
+}
+
+// ---- 1. compaction (query order) + normalisation: P[0 .. n) in LDS; returns n = min(*n_all,
+//         MAXP), *n_all = the pair's correspondences.  Ends with a barrier. ----
+__device__ __forceinline__ int gather_pairs(const PoseArgs &a, int b, int n_in, const float *__restrict__ pts0,
+                                            const float *__restrict__ pts1, const int *__restrict__ match_idx,
+                                            const float *__restrict__ kp1, float4 *P, int *wsum, int *n_all) {
+    const int t = threadIdx.x;
     const int per = (n_in + NT - 1) / NT;
     const int i0 = t * per, i1 = min(i0 + per, n_in);
+    auto normalised = [&](float x1, float y1, float x2, float y2) {
+        return make_float4((x1 - a.cx) / a.fx, (y1 - a.cy) / a.fy, (x2 - a.cx) / a.fx, (y2 - a.cy) / a.fy);
+    };
     int cnt = 0;
-    // a match index outside [0, cap) is "no match" (never dereferenced).  Up to PF_PER
-    // entries per thread (cap <= 4 NT) are loaded, gathered and normalised here, before the
-    // scan, so their load latency overlaps it instead of costing a second dependent pass.
+    // Up to PF_PER entries per thread (cap <= 4 NT) are loaded, gathered and normalised here, before
+    // the scan, so their load latency overlaps it instead of costing a second dependent pass.
     constexpr int PF_PER = 4;
     float4 pf[PF_PER];
     bool pok[PF_PER];
@@ -420,41 +487,16 @@ __global__ __launch_bounds__(NT, PE_WAVES) void k_pose_ransac(PoseArgs a, const 
 #pragma unroll
         for (int q = 0; q < PF_PER; q++) {
             const int i = i0 + q;
-            pok[q] = false;
-            pf[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (i >= i1) continue;
-            const size_t gi = (size_t)b * a.cap + i;
-            float x2, y2;
-            if (match_idx) {
-                const int j = match_idx[gi];
-                if ((unsigned)j >= (unsigned)a.cap) continue;
-                x2 = kp1[((size_t)b * a.cap + j) * 2];
-                y2 = kp1[((size_t)b * a.cap + j) * 2 + 1];
-            } else {
-                x2 = pts1[gi * 2];
-                y2 = pts1[gi * 2 + 1];
-            }
-            const float x1 = pts0[gi * 2], y1 = pts0[gi * 2 + 1];
-            pf[q] = make_float4((x1 - a.cx) / a.fx, (y1 - a.cy) / a.fy, (x2 - a.cx) / a.fx, (y2 - a.cy) / a.fy);
-            pok[q] = true;
-            cnt++;
+            float x1, y1, x2, y2;
+            pok[q] = i < i1 && mv::load_pair(b, a.cap, i, pts0, pts1, match_idx, kp1, x1, y1, x2, y2);
+            pf[q] = pok[q] ? normalised(x1, y1, x2, y2) : make_float4(0.f, 0.f, 0.f, 0.f);
+            cnt += pok[q] ? 1 : 0;
         }
     } else {
         for (int i = i0; i < i1; i++)
             cnt += (!match_idx || (unsigned)match_idx[(size_t)b * a.cap + i] < (unsigned)a.cap) ? 1 : 0;
     }
-    int x = cnt;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        int y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) wsum[w] = x;
-    __syncthreads();
-    int off = x - cnt;
-    for (int k = 0; k < w; k++) off += wsum[k];
-    const int n_all = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    const int n = min(n_all, MAXP);
+    int off = scan_excl_256_one_barrier(cnt, n_all, wsum);
     if (per <= PF_PER) {
 #pragma unroll
         for (int q = 0; q < PF_PER; q++) {
@@ -464,602 +506,632 @@ __global__ __launch_bounds__(NT, PE_WAVES) void k_pose_ransac(PoseArgs a, const 
         }
     } else {
         for (int i = i0; i < i1; i++) {
-            float x1 = pts0[((size_t)b * a.cap + i) * 2], y1 = pts0[((size_t)b * a.cap + i) * 2 + 1], x2, y2;
-            if (match_idx) {
-                const int j = match_idx[(size_t)b * a.cap + i];
-                if ((unsigned)j >= (unsigned)a.cap) continue;
-                x2 = kp1[((size_t)b * a.cap + j) * 2];
-                y2 = kp1[((size_t)b * a.cap + j) * 2 + 1];
-            } else {
-                x2 = pts1[((size_t)b * a.cap + i) * 2];
-                y2 = pts1[((size_t)b * a.cap + i) * 2 + 1];
-            }
-            if (off < MAXP)
-                P[off] = make_float4((x1 - a.cx) / a.fx, (y1 - a.cy) / a.fy, (x2 - a.cx) / a.fx, (y2 - a.cy) / a.fy);
+            float x1, y1, x2, y2;
+            if (!mv::load_pair(b, a.cap, i, pts0, pts1, match_idx, kp1, x1, y1, x2, y2)) continue;
+            if (off < MAXP) P[off] = normalised(x1, y1, x2, y2);
             off++;
         }
     }
     __syncthreads();
-    float *To = T + (size_t)b * 12;
-    if (n < 8) {
-        if (t < 12) To[t] = (t % 4 == t / 4) ? 1.f : 0.f;
-        if (t == 0) {
-            num_inliers[b] = 0;
-            if (num_matches) num_matches[b] = n_all;
-            status[b] = n_all == 0 ? MV_ERR_NO_POINTS : MV_ERR_DEGENERATE;
-        }
-        return;
-    }
+    return min(*n_all, MAXP);
+}
 
-    // ---- 2. hypotheses, preemptively MSAC-scored (sum of min(Sampson^2, thr^2); plain
-    //         inlier counting cannot separate an outlier-contaminated 8-point solution that
-    //         still explains every inlier within the band -- near-pure forward motion).
-    //         Every hypothesis is scored on an evenly strided subset of PRE_M
-    //         correspondences; the SURV best of each wave survive (preemptive RANSAC,
-    //         Nister 2003) and are re-scored on all correspondences cooperatively. ----
-    constexpr int PRE_M = PE_PREM, SURV = 2, NS = 4 * SURV;
-    const int m = min(n, PRE_M);
+// 8 distinct indices in [0, n) from the counter-based stream at `base`; false: not found in 64 draws.
+// Drawn into a local array and copied out: drawn through the reference, the compiler carries the 8
+// indices from one hypothesis to the next (17 more VGPRs live in the hypothesis loop).
+__device__ __forceinline__ bool draw8(unsigned long long base, int n, int (&out)[8]) {
+    int idx[8];
+    int drawn = 0;
+    unsigned long long r = 0;
+    for (int d = 0; d < 64 && drawn < 8; d++) {  // two 32-bit draws per splitmix64 output
+        if ((d & 1) == 0) r = splitmix64(base + (d >> 1));
+        const unsigned u = (d & 1) ? (unsigned)r : (unsigned)(r >> 32);
+        const int c = (int)(((unsigned long long)u * (unsigned)n) >> 32);
+        bool dup = false;
+#pragma unroll
+        for (int q = 0; q < 8; q++) dup |= (q < drawn) && idx[q] == c;
+        if (!dup) {
+#pragma unroll
+            for (int q = 0; q < 8; q++)
+                if (q == drawn) idx[q] = c;
+            drawn++;
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 8; q++) out[q] = idx[q];
+    return drawn == 8;
+}
+
+// MSAC cost of e on the scoring subset of m points (pairs from sub; an odd last one from P)
+__device__ __forceinline__ float prem_cost(const float (&e)[9], const float4 (*sub)[2], const float4 *P, int m,
+                                           unsigned step16, float thr2) {
+    f2v acc = {0.f, 0.f};
+    const int m2 = m / 2;
+    int k = 0;
+    for (; k + 2 <= m2; k += 2) {  // 4 LDS broadcast reads in flight per step
+        const float4 A0 = sub[k][0], B0 = sub[k][1], A1 = sub[k + 1][0], B1 = sub[k + 1][1];
+        acc += msac_cost2(e, A0, B0, thr2);
+        acc += msac_cost2(e, A1, B1, thr2);
+    }
+    if (k < m2) acc += msac_cost2(e, sub[k][0], sub[k][1], thr2);
+    float cost = acc.x + acc.y;
+    if (m & 1) {
+        int c = 0;
+        cost += msac_cost(e, P[((m - 1) * step16) >> 16], thr2, c);
+    }
+    return cost;
+}
+
+// a thread's best hypothesis so far: the lowest (cost, id)
+struct Hyp {
+    float cost = __builtin_inff();
+    int h = 0x7fffffff;  // none yet
+    float e[9];
+};
+
+// ---- 2. hypotheses, preemptively MSAC-scored (sum of min(Sampson^2, thr^2); plain inlier counting
+//         cannot separate an outlier-contaminated 8-point solution that still explains every
+//         inlier within the band -- near-pure forward motion).  Every hypothesis is scored on an
+//         evenly strided subset of PE_PREM correspondences; the SURV best of each wave survive
+//         (preemptive RANSAC, Nister 2003) and are re-scored on all correspondences (3). ----
+__device__ __forceinline__ void score_hypotheses(const PoseArgs &a, int b, const float4 *P, int n, PoseLds &s,
+                                                 Hyp &best) {
+    const int t = threadIdx.x;
+    const int m = min(n, PE_PREM);
     const unsigned step16 = ((unsigned)n << 16) / (unsigned)m;  // subset point k: (k * step16) >> 16 < n
-    // the subset in point-pair layout (points 2k, 2k+1 of it in s_sub[k])
-    __shared__ float4 s_sub[PRE_M / 2][2];
     if (t < m / 2) {
         const float4 pa = P[((2 * t) * step16) >> 16], pb = P[((2 * t + 1) * step16) >> 16];
-        s_sub[t][0] = make_float4(pa.x, pb.x, pa.y, pb.y);
-        s_sub[t][1] = make_float4(pa.z, pb.z, pa.w, pb.w);
+        s.sub[t][0] = make_float4(pa.x, pb.x, pa.y, pb.y);
+        s.sub[t][1] = make_float4(pa.z, pb.z, pa.w, pb.w);
     }
     __syncthreads();
-    float best_cost = __builtin_inff();
-    int best_h = 0x7fffffff;
-    float best_e[9];
     for (int h = t; h < a.hypotheses; h += NT) {
         int idx[8];
-        const unsigned long long base = a.seed ^ ((unsigned long long)b << 40) ^ ((unsigned long long)h << 8);
-        int drawn = 0;
-        unsigned long long r = 0;
-        for (int d = 0; d < 64 && drawn < 8; d++) {  // two 32-bit draws per splitmix64 output
-            if ((d & 1) == 0) r = splitmix64(base + (d >> 1));
-            const unsigned u = (d & 1) ? (unsigned)r : (unsigned)(r >> 32);
-            const int c = (int)(((unsigned long long)u * (unsigned)n) >> 32);
-            bool dup = false;
-#pragma unroll
-            for (int q = 0; q < 8; q++) dup |= (q < drawn) && idx[q] == c;
-            if (!dup) {
-#pragma unroll
-                for (int q = 0; q < 8; q++)
-                    if (q == drawn) idx[q] = c;
-                drawn++;
-            }
-        }
-        if (drawn < 8) continue;
         float e[9];
+        if (!draw8(a.seed ^ ((unsigned long long)b << 40) ^ ((unsigned long long)h << 8), n, idx)) continue;
         if (!eight_point(P, idx, e)) continue;
-        f2v acc = {0.f, 0.f};
-        const int m2 = m / 2;
-        int k = 0;
-        for (; k + 2 <= m2; k += 2) {  // 4 LDS broadcast reads in flight per step
-            const float4 A0 = s_sub[k][0], B0 = s_sub[k][1], A1 = s_sub[k + 1][0], B1 = s_sub[k + 1][1];
-            acc += msac_cost2(e, A0, B0, a.thr2);
-            acc += msac_cost2(e, A1, B1, a.thr2);
-        }
-        if (k < m2) acc += msac_cost2(e, s_sub[k][0], s_sub[k][1], a.thr2);
-        float cost = acc.x + acc.y;
-        if (m & 1) {
-            int c = 0;
-            cost += msac_cost(e, P[((m - 1) * step16) >> 16], a.thr2, c);
-        }
-        if (cost < best_cost || (cost == best_cost && h < best_h)) {
-            best_cost = cost;
-            best_h = h;
+        const float cost = prem_cost(e, s.sub, P, m, step16, a.thr2);
+        if (cost < best.cost || (cost == best.cost && h < best.h)) {
+            best.cost = cost;
+            best.h = h;
 #pragma unroll
-            for (int r = 0; r < 9; r++) best_e[r] = e[r];
+            for (int r = 0; r < 9; r++) best.e[r] = e[r];
         }
     }
-    // ---- 3. survivors: the SURV lowest (partial cost, hypothesis id) keys of each wave (cost
-    //         >= 0, so its bits order as uint), then full MSAC of the NS survivors ----
-    __shared__ int s_sh[NS];
-    __shared__ float s_sE[NS][9];
-    {
-        unsigned long long key = best_h == 0x7fffffff
-                                     ? ~0ull
-                                     : ((unsigned long long)__float_as_uint(best_cost) << 32) | (unsigned)best_h;
-        for (int r = 0; r < SURV; r++) {
-            unsigned long long k = key;
+}
+
+// ---- 3. survivors: the SURV lowest (partial cost, hypothesis id) keys of each wave (cost >= 0, so
+//         its bits order as uint) into s.sh / s.sE ----
+__device__ __forceinline__ void keep_wave_survivors(const Hyp &best, PoseLds &s) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    unsigned long long key =
+        best.h == 0x7fffffff ? ~0ull : ((unsigned long long)__float_as_uint(best.cost) << 32) | (unsigned)best.h;
+    for (int r = 0; r < SURV; r++) {
+        const unsigned long long k = wave::wave_min_u64(key);
+        if (k == ~0ull) {
+            if (lane == 0) s.sh[w * SURV + r] = -1;
+        } else if (key == k) {  // the owner (keys are unique: hypothesis ids differ)
+            s.sh[w * SURV + r] = best.h;
 #pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const unsigned long long k2 = __shfl_xor(k, o, 64);
-                k = k2 < k ? k2 : k;
-            }
-            if (k == ~0ull) {
-                if (lane == 0) s_sh[w * SURV + r] = -1;
-            } else if (key == k) {  // the owner (keys are unique: hypothesis ids differ)
-                s_sh[w * SURV + r] = best_h;
-#pragma unroll
-                for (int q = 0; q < 9; q++) s_sE[w * SURV + r][q] = best_e[q];
-                key = ~0ull;
-            }
+            for (int q = 0; q < 9; q++) s.sE[w * SURV + r][q] = best.e[q];
+            key = ~0ull;
         }
     }
-    __syncthreads();
-    float cs[NS];
-    int cn[NS];
+}
+
+// full MSAC of the NS survivors by the whole block: wave partials of cost and inliers into s.red2
+__device__ __forceinline__ void rescore_survivors(const PoseArgs &a, const float4 *P, int n, PoseLds &s) {
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    float v[2 * NS];  // costs, then inlier counts
 #pragma unroll
     for (int sv = 0; sv < NS; sv += 2) {  // two survivors per packed instruction
         f2v E2[9];
 #pragma unroll
-        for (int q = 0; q < 9; q++) E2[q] = f2v{s_sE[sv][q], s_sE[sv + 1][q]};
+        for (int q = 0; q < 9; q++) E2[q] = f2v{s.sE[sv][q], s.sE[sv + 1][q]};
         f2v acc = {0.f, 0.f};
         int na = 0, nb = 0;
-        if (s_sh[sv] >= 0 || s_sh[sv + 1] >= 0)
+        if (s.sh[sv] >= 0 || s.sh[sv + 1] >= 0)
             for (int i = t; i < n; i += NT) acc += msac_cost2h(E2, P[i], a.thr2, na, nb);
-        cs[sv] = s_sh[sv] >= 0 ? acc.x : 0.f;
-        cs[sv + 1] = s_sh[sv + 1] >= 0 ? acc.y : 0.f;
-        cn[sv] = s_sh[sv] >= 0 ? na : 0;
-        cn[sv + 1] = s_sh[sv + 1] >= 0 ? nb : 0;
+        v[sv] = s.sh[sv] >= 0 ? acc.x : 0.f;
+        v[sv + 1] = s.sh[sv + 1] >= 0 ? acc.y : 0.f;
+        v[NS + sv] = (float)(s.sh[sv] >= 0 ? na : 0);
+        v[NS + sv + 1] = (float)(s.sh[sv + 1] >= 0 ? nb : 0);
     }
-    __shared__ float s_red2[4][2 * NS];
-    {
-        float v[2 * NS];
 #pragma unroll
-        for (int sv = 0; sv < NS; sv++) {
-            v[sv] = cs[sv];
-            v[NS + sv] = (float)cn[sv];
-        }
+    for (int k = 0; k < 2 * NS; k++) v[k] = wave_sum(v[k]);
+    if (lane == 0) {
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-            for (int k = 0; k < 2 * NS; k++) v[k] += __shfl_xor(v[k], o, 64);
-        }
-        if (lane == 0) {
-#pragma unroll
-            for (int k = 0; k < 2 * NS; k++) s_red2[w][k] = v[k];
-        }
+        for (int k = 0; k < 2 * NS; k++) s.red2[w][k] = v[k];
     }
-    __syncthreads();
-    // ---- 3b. the two lowest (full cost, hypothesis id) survivors are the starts of the
-    //         refinement (below), and the refined pose with the lower robust cost wins.  Under pixel noise one start is not enough: the robust cost has local
-    //         minima along the rotation / translation-direction ambiguity of forward motion and
-    //         the best 8-point sample's pose can sit in one (the same algorithm on the CPU,
-    //         0.5-1 px noise, 30 % outliers: single starts end 2-7 deg off in translation
-    //         direction where the fit from the true pose is within 0.5; two starts: <= 1.6). ----
-    __shared__ float s_E[2][9];
-    __shared__ int s_nh;  // starts found (0, 1, 2)
-    __shared__ bool s_exact;
-    if (t == 0) {
-        int b0 = -1, b1 = -1;
-        float c0 = 0.f, c1 = 0.f;
-        for (int sv = 0; sv < NS; sv++) {
-            if (s_sh[sv] < 0) continue;
-            const float c = s_red2[0][sv] + s_red2[1][sv] + s_red2[2][sv] + s_red2[3][sv];
-            if (b0 < 0 || c < c0 || (c == c0 && s_sh[sv] < s_sh[b0])) {
-                b1 = b0;
-                c1 = c0;
-                b0 = sv;
-                c0 = c;
-            } else if (b1 < 0 || c < c1 || (c == c1 && s_sh[sv] < s_sh[b1])) {
-                b1 = sv;
-                c1 = c;
-            }
-        }
-        s_nh = b0 < 0 ? 0 : (b1 < 0 ? 1 : 2);
-        // the best survivor's inliers fit (almost) exactly: sum of inlier r^2 = its MSAC cost
-        // minus thr^2 per outlier, below 1e-3 thr^2 per inlier (exact projections: ~1e-12;
-        // 0.5 px noise: ~0.2) -- the first start will likely be an exact fit
-        if (b0 >= 0) {
-            const float na0 = s_red2[0][NS + b0] + s_red2[1][NS + b0] + s_red2[2][NS + b0] + s_red2[3][NS + b0];
-            s_exact = c0 - ((float)n - na0) * a.thr2 <= 1e-3f * na0 * a.thr2;
-        }
-        if (b0 >= 0)
-            for (int r = 0; r < 9; r++) {
-                s_E[0][r] = s_sE[b0][r];
-                s_E[1][r] = s_sE[b1 >= 0 ? b1 : b0][r];
-            }
-    }
-    __syncthreads();
-    if (s_nh == 0) {
-        if (t < 12) To[t] = (t % 4 == t / 4) ? 1.f : 0.f;
-        if (t == 0) {
-            num_inliers[b] = 0;
-            if (num_matches) num_matches[b] = n_all;
-            status[b] = MV_ERR_DEGENERATE;
-        }
-        return;
-    }
-    // ---- 4-6, per start: decomposition + cheirality, robust Gauss-Newton, the robust cost of
-    //      the refined pose.  Two schedules over groups of waves, block-uniform:
-    //      - sequential (one group = the block): the starts one after the other, the second only
-    //        when the first did not reach an exact fit -- exact data costs one refinement;
-    //      - concurrent (two groups = the block's halves, waves 0-1 and 2-3): when two starts
-    //        exist and the best survivor's inliers are not an exact fit (noisy data, where both
-    //        starts are refined anyway), each half refines one start, so the two Gauss-Newton
-    //        chains share their barriers instead of running back to back.
-    //      Every barrier is block-wide: a group that has converged keeps arriving at them. ----
-    __shared__ float s_cand[2][4][12];
-    __shared__ float s_uv[2][2][3][3];
-    __shared__ int s_votes[4][4];  // [wave][candidate]
-    __shared__ float s_red[2][4][22];
-    __shared__ float s_state[2][2][16];  // [iteration parity][group]
-    __shared__ float s_fin[4];
-    __shared__ int s_fin_n[4];
-    static_assert(MAXP <= 32 * (NT / 2), "the inlier mask holds 32 correspondences per thread of a half");
-    const float th_max = sqrtf(a.thr2), th_min = 0.01f * th_max, r_cap = 3.f * th_max;
-    float bR[9], bT[3], bcost = __builtin_inff();
-    int bn = 0;
-    // the schedule as a compile-time parameter: each gets its own code (constant strides)
-    auto refine = [&](auto par_c) {
-    constexpr bool par = decltype(par_c)::value;
-    constexpr int G = par ? NT / 2 : NT;       // threads per group
-    const int gid = par ? (w >> 1) : 0;        // this thread's group
-    const int gt = par ? (t & (NT / 2 - 1)) : t;
-    const int gw0 = par ? 2 * gid : 0;         // the group's first wave
-    constexpr int gnw = par ? 2 : 4;           // its waves
-    const int rounds = par ? 1 : s_nh;
-    for (int rd = 0; rd < rounds; rd++) {
-        const int sti = par ? gid : rd;
-        float E[9];
-        for (int r = 0; r < 9; r++) E[r] = s_E[sti][r];
-        if (gt == 0) {
-            float U[3][3], V[3][3];
-            essential_uv(E, U, V);
-            for (int i = 0; i < 3; i++)
-                for (int j = 0; j < 3; j++) {
-                    s_uv[gid][0][i][j] = U[i][j];
-                    s_uv[gid][1][i][j] = V[i][j];
-                }
-        }
-        __syncthreads();
-        if (gt < 4) {  // candidate c = gt, one lane each
-            const float W[3][3] = {{0, -1, 0}, {1, 0, 0}, {0, 0, 1}};
-            float U[3][3], V[3][3];
-            for (int i = 0; i < 3; i++)
-                for (int j = 0; j < 3; j++) {
-                    U[i][j] = s_uv[gid][0][i][j];
-                    V[i][j] = s_uv[gid][1][i][j];
-                }
-            const int c = gt;
-            float R[3][3];
-            for (int i = 0; i < 3; i++)
-                for (int j = 0; j < 3; j++) {
-                    float s = 0;
-                    for (int k = 0; k < 3; k++) {
-                        float uw = 0;
-                        for (int l = 0; l < 3; l++) uw += U[i][l] * (c < 2 ? W[l][k] : W[k][l]);
-                        s += uw * V[j][k];
-                    }
-                    R[i][j] = s;
-                }
-            const float sg = (c & 1) ? -1.f : 1.f;
-            for (int i = 0; i < 9; i++) s_cand[gid][c][i] = R[i / 3][i % 3];
-            for (int i = 0; i < 3; i++) s_cand[gid][c][9 + i] = sg * U[i][2];
-        }
-        __syncthreads();
-        int votes[4] = {0, 0, 0, 0};
-        unsigned inl_mask = 0;  // bit k: correspondence gt + k G is a Sampson inlier of E
-        for (int i = gt, k = 0; i < n; i += G, k++)
-            inl_mask |= sampson_inlier(E, P[i], a.thr2) ? 1u << k : 0u;
-#pragma unroll
-        for (int c = 0; c < 4; c++) {  // candidate-outer: 12 candidate floats live, not 48
-            for (unsigned mk = inl_mask; mk; mk &= mk - 1) {
-                const float4 p = P[gt + __builtin_ctz(mk) * G];
-                // depths z1, z2 of the midpoint triangulation, q z1 + t = -m z2 in the least-
-                // squares sense: z = num / det with det > 0, so only the numerators' signs count
-                const float *C = s_cand[gid][c];
-                const F3 q = {{C[0] * p.x + C[1] * p.y + C[2], C[3] * p.x + C[4] * p.y + C[5], C[6] * p.x + C[7] * p.y + C[8]}};
-                const F3 m = {{-p.z, -p.w, -1.f}};
-                const F3 tt = {{C[9], C[10], C[11]}};
-                const float aa = dot3(q, q), ab = dot3(q, m), bb = dot3(m, m);
-                const float ra = -dot3(q, tt), rb = -dot3(m, tt);
-                const float det = aa * bb - ab * ab;
-                const float n1 = ra * bb - ab * rb, n2 = aa * rb - ab * ra;
-                votes[c] += (det > 0.f && n1 > 0.f && n2 > 0.f) ? 1 : 0;
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < 4; c++) {
-            int v = votes[c];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-            if (lane == 0) s_votes[w][c] = v;
-        }
-        __syncthreads();
-        auto gsum_votes = [&](int c) {
-            int v = 0;
-            for (int k = 0; k < gnw; k++) v += s_votes[gw0 + k][c];
-            return v;
-        };
-        int bc = 0, bv = gsum_votes(0);
-        for (int c = 1; c < 4; c++) {
-            const int v = gsum_votes(c);
-            if (v > bv) {
-                bv = v;
-                bc = c;
-            }
-        }
+}
 
-        // ---- robust Gauss-Newton: iteratively reweighted, Cauchy weights 1 / (1 + (r / c)^2)
-        //      on the Sampson residuals below 3 thr (none above), the scale c_0 = thr,
-        //      c_{k+1} = min(thr, max(2 rms_w, 0.01 thr)) (rms_w: the weighted rms of iteration
-        //      k): on exact data c shrinks until the outliers that fell inside the band no
-        //      longer pull (converges to machine precision), on noisy data it settles near
-        //      2 sigma.  Weights and Sampson denominators are frozen within an iteration.  The
-        //      group's first wave solves the 5x5 normal equations from the group's 22 sums; one
-        //      block barrier per iteration after the sums, one after the state (both
-        //      double-buffered). ----
-        float R[9], tv[3], bs[6];
+// ---- 3b. one thread: the two lowest (full cost, hypothesis id) survivors are the starts of the
+//         refinement, and the refined pose with the lower robust cost wins.  Two, because under
+//         pixel noise the best 8-point sample's pose can sit in a local minimum of the robust cost
+//         along forward motion's rotation / translation-direction ambiguity. ----
+__device__ __forceinline__ void pick_starts(const PoseArgs &a, int n, PoseLds &s) {
+    int b0 = -1, b1 = -1;
+    float c0 = 0.f, c1 = 0.f;
+    for (int sv = 0; sv < NS; sv++) {
+        if (s.sh[sv] < 0) continue;
+        const float c = s.red2[0][sv] + s.red2[1][sv] + s.red2[2][sv] + s.red2[3][sv];
+        if (b0 < 0 || c < c0 || (c == c0 && s.sh[sv] < s.sh[b0])) {
+            b1 = b0;
+            c1 = c0;
+            b0 = sv;
+            c0 = c;
+        } else if (b1 < 0 || c < c1 || (c == c1 && s.sh[sv] < s.sh[b1])) {
+            b1 = sv;
+            c1 = c;
+        }
+    }
+    s.nh = b0 < 0 ? 0 : (b1 < 0 ? 1 : 2);
+    // the best survivor's inliers fit (almost) exactly: sum of inlier r^2 = its MSAC cost
+    // minus thr^2 per outlier, below 1e-3 thr^2 per inlier (exact projections: ~1e-12;
+    // 0.5 px noise: ~0.2) -- the first start will likely be an exact fit
+    if (b0 >= 0) {
+        const float na0 = s.red2[0][NS + b0] + s.red2[1][NS + b0] + s.red2[2][NS + b0] + s.red2[3][NS + b0];
+        s.exact = c0 - ((float)n - na0) * a.thr2 <= 1e-3f * na0 * a.thr2;
+    }
+    if (b0 >= 0)
+        for (int r = 0; r < 9; r++) {
+            s.E[0][r] = s.sE[b0][r];
+            s.E[1][r] = s.sE[b1 >= 0 ? b1 : b0][r];
+        }
+}
+
+// ---- 4-6: the refinement of the starts.  Two schedules over groups of waves, block-uniform:
+//      - sequential (par = false, one group = the block): the starts one after the other, the second
+//        only when the first did not reach an exact fit -- exact data costs one refinement;
+//      - concurrent (par = true, two groups = the block's halves, waves 0-1 and 2-3): when two
+//        starts exist and the best survivor's inliers are not an exact fit (noisy data, where both
+//        starts are refined anyway), each half refines one start, so the two Gauss-Newton chains
+//        share their barriers instead of running back to back.
+//      Every barrier is block-wide: a group that has converged keeps arriving at them.  The
+//      schedule is a compile-time parameter: each gets its own code (constant strides). ----
+template <bool par>
+struct Group {
+    static constexpr int G = par ? NT / 2 : NT;  // threads per group
+    static constexpr int gnw = par ? 2 : 4;      // its waves
+    int gid, gt, gw0;                            // this thread's group, its index in it, the group's first wave
+    __device__ __forceinline__ Group()
+        : gid(par ? (int)(threadIdx.x >> 7) : 0),
+          gt(par ? (int)(threadIdx.x & (NT / 2 - 1)) : (int)threadIdx.x),
+          gw0(par ? 2 * gid : 0) {}
+};
+
+// the Cauchy scale's range and the residual cap, from the inlier threshold
+struct Scales {
+    float th_max, th_min, r_cap;
+    __device__ __forceinline__ explicit Scales(float thr2)
+        : th_max(sqrtf(thr2)), th_min(0.01f * th_max), r_cap(3.f * th_max) {}
+};
+
+// the best refined pose so far (the same in every thread)
+struct Refined {
+    float R[9], t[3], cost = __builtin_inff();
+    int inliers = 0;
+};
+
+// ---- 4a. E -> the four (R, t) candidates of the group into s.cand[gid].  Two barriers. ----
+template <bool par>
+__device__ __forceinline__ void decompose_start(const float (&E)[9], const Group<par> &g, PoseLds &s) {
+    if (g.gt == 0) {
+        float U[3][3], V[3][3];
+        essential_uv(E, U, V);
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) {
+                s.uv[g.gid][0][i][j] = U[i][j];
+                s.uv[g.gid][1][i][j] = V[i][j];
+            }
+    }
+    __syncthreads();
+    if (g.gt < 4) {  // candidate c = gt, one lane each
+        const float W[3][3] = {{0, -1, 0}, {1, 0, 0}, {0, 0, 1}};
+        float U[3][3], V[3][3];
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) {
+                U[i][j] = s.uv[g.gid][0][i][j];
+                V[i][j] = s.uv[g.gid][1][i][j];
+            }
+        const int c = g.gt;
+        float R[3][3];
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) {
+                float sum = 0;
+                for (int k = 0; k < 3; k++) {
+                    float uw = 0;
+                    for (int l = 0; l < 3; l++) uw += U[i][l] * (c < 2 ? W[l][k] : W[k][l]);
+                    sum += uw * V[j][k];
+                }
+                R[i][j] = sum;
+            }
+        const float sg = (c & 1) ? -1.f : 1.f;
+        for (int i = 0; i < 9; i++) s.cand[g.gid][c][i] = R[i / 3][i % 3];
+        for (int i = 0; i < 3; i++) s.cand[g.gid][c][9 + i] = sg * U[i][2];
+    }
+    __syncthreads();
+}
+
+// ---- 4b. cheirality: the candidate with the most Sampson inliers of E in front of both cameras
+//         (the same in every thread of the group).  One barrier. ----
+template <bool par>
+__device__ __forceinline__ int cheirality_vote(const float (&E)[9], const float4 *P, int n, float thr2,
+                                               const Group<par> &g, PoseLds &s) {
+    static_assert(MAXP <= 32 * (NT / 2), "the inlier mask holds 32 correspondences per thread of a half");
+    constexpr int G = Group<par>::G;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int votes[4] = {0, 0, 0, 0};
+    unsigned inl_mask = 0;  // bit k: correspondence gt + k G is a Sampson inlier of E
+    for (int i = g.gt, k = 0; i < n; i += G, k++) inl_mask |= sampson_inlier(E, P[i], thr2) ? 1u << k : 0u;
 #pragma unroll
-        for (int i = 0; i < 9; i++) R[i] = s_cand[gid][bc][i];
+    for (int c = 0; c < 4; c++) {  // candidate-outer: 12 candidate floats live, not 48
+        for (unsigned mk = inl_mask; mk; mk &= mk - 1) {
+            const float4 p = P[g.gt + __builtin_ctz(mk) * G];
+            // depths z1, z2 of the midpoint triangulation, q z1 + t = -m z2 in the least-
+            // squares sense: z = num / det with det > 0, so only the numerators' signs count
+            const float *C = s.cand[g.gid][c];
+            const F3 q = {{C[0] * p.x + C[1] * p.y + C[2], C[3] * p.x + C[4] * p.y + C[5], C[6] * p.x + C[7] * p.y + C[8]}};
+            const F3 m = {{-p.z, -p.w, -1.f}};
+            const F3 tt = {{C[9], C[10], C[11]}};
+            const float aa = dot3(q, q), ab = dot3(q, m), bb = dot3(m, m);
+            const float ra = -dot3(q, tt), rb = -dot3(m, tt);
+            const float det = aa * bb - ab * ab;
+            const float n1 = ra * bb - ab * rb, n2 = aa * rb - ab * ra;
+            votes[c] += (det > 0.f && n1 > 0.f && n2 > 0.f) ? 1 : 0;
+        }
+    }
 #pragma unroll
-        for (int i = 0; i < 3; i++) tv[i] = s_cand[gid][bc][9 + i];
-        tangent_basis_f(tv, bs);
+    for (int c = 0; c < 4; c++) {
+        const int v = wave_sum(votes[c]);
+        if (lane == 0) s.votes[w][c] = v;
+    }
+    __syncthreads();
+    int bc = 0, bv = 0;
+    for (int c = 0; c < 4; c++) {
+        int v = 0;
+        for (int k = 0; k < g.gnw; k++) v += s.votes[g.gw0 + k][c];
+        if (c == 0 || v > bv) {
+            bv = v;
+            bc = c;
+        }
+    }
+    return bc;
+}
+
+// ---- 5a. one Gauss-Newton pass over correspondences i0, i0 + G, ... < n: acc = sum w J^T J (15,
+//         upper), sum w J^T r (5), sum w r^2, sum w, with Cauchy weights at scale 1 / rcs ----
+__device__ __forceinline__ void gn_accumulate(const float4 *P, int i0, int n, int G, const float (&R)[9],
+                                              const float (&tv)[3], const float (&bs)[6], float rcs, float r_cap,
+                                              float (&acc)[22]) {
+#pragma unroll
+    for (int k = 0; k < 22; k++) acc[k] = 0.f;
+    for (int i = i0; i < n; i += G) {
+        const float4 p = P[i];
+        const float x2[3] = {p.z, p.w, 1.f};
+        float q[3], x2t[3], e, s2;
+        pose_sampson(R, tv, p, q, x2t, e, s2);
+        if (!(s2 > 0.f)) continue;
+        const float inv = __builtin_amdgcn_rsqf(s2);  // native: a GN weight, not an output
+        const float r = e * inv;                      // Sampson distance
+        if (!(fabsf(r) < r_cap)) continue;
+        const float u = r * rcs;
+        const float wt = __builtin_amdgcn_rcpf(1.f + u * u);
+        // d e / d omega = q x (x2 x t)  (R <- exp(omega) R);  d e / d t = q x x2
+        const float dw[3] = {q[1] * x2t[2] - q[2] * x2t[1], q[2] * x2t[0] - q[0] * x2t[2],
+                             q[0] * x2t[1] - q[1] * x2t[0]};
+        const float dt[3] = {q[1] * x2[2] - q[2] * x2[1], q[2] * x2[0] - q[0] * x2[2],
+                             q[0] * x2[1] - q[1] * x2[0]};
+        const float J[5] = {dw[0] * inv, dw[1] * inv, dw[2] * inv,
+                            (dt[0] * bs[0] + dt[1] * bs[1] + dt[2] * bs[2]) * inv,
+                            (dt[0] * bs[3] + dt[1] * bs[4] + dt[2] * bs[5]) * inv};
+        float Jw[5];
+#pragma unroll
+        for (int v = 0; v < 5; v++) Jw[v] = J[v] * wt;
+        int k = 0;
+#pragma unroll
+        for (int v = 0; v < 5; v++) {
+#pragma unroll
+            for (int x = v; x < 5; x++) acc[k++] += Jw[v] * J[x];
+        }
+#pragma unroll
+        for (int v = 0; v < 5; v++) acc[15 + v] += Jw[v] * r;
+        acc[20] += wt * r * r;
+        acc[21] += wt;
+    }
+}
+
+// d = -(H (1 + 1e-6) + 1e-30 I)^-1 g for the 5x5 SPD H given as its upper triangle (15, row-major):
+// float Cholesky on the native reciprocal square root (the step only has to be a descent
+// direction); every loop fully unrolled: static register indexing.  false: not positive definite
+__device__ __forceinline__ bool chol5_step(const float (&H)[15], const float (&g)[5], float (&d)[5]) {
+    float A[5][5];
+#pragma unroll
+    for (int v = 0, k = 0; v < 5; v++)
+#pragma unroll
+        for (int x = v; x < 5; x++, k++) {
+            A[v][x] = H[k];
+            A[x][v] = H[k];
+        }
+#pragma unroll
+    for (int v = 0; v < 5; v++) A[v][v] = A[v][v] * (1.0f + 1e-6f) + 1e-30f;
+    float L[5][5] = {}, rl[5] = {};
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < 5; i++)
+#pragma unroll
+        for (int j = 0; j <= i; j++) {
+            float sum = A[i][j];
+#pragma unroll
+            for (int m = 0; m < j; m++) sum -= L[i][m] * L[j][m];
+            if (i == j) {
+                ok = ok && sum > 0.f;
+                rl[i] = __builtin_amdgcn_rsqf(fmaxf(sum, 1e-30f));  // 1 / L[i][i]
+                L[i][i] = fmaxf(sum, 1e-30f) * rl[i];
+            } else {
+                L[i][j] = sum * rl[j];
+            }
+        }
+    float y[5];
+#pragma unroll
+    for (int i = 0; i < 5; i++) {
+        float sum = -g[i];
+#pragma unroll
+        for (int m = 0; m < i; m++) sum -= L[i][m] * y[m];
+        y[i] = sum * rl[i];
+    }
+#pragma unroll
+    for (int i = 4; i >= 0; i--) {
+        float sum = y[i];
+#pragma unroll
+        for (int m = i + 1; m < 5; m++) sum -= L[m][i] * d[m];
+        d[i] = sum * rl[i];
+    }
+    return ok;
+}
+
+// ---- 5b. the group's first wave: the group's 22 sums from its GNW waves' partials (red[0 .. GNW)),
+//         the 5x5 solve, R <- exp(omega) R, t <- normalise(t + B d), the next Cauchy scale, and the
+//         state st[14]: R (9), t (3), scale, flags (bit 0: failed or stopped -- keep the old
+//         state; bit 1: converged).  live: this group still iterates. ----
+template <int GNW>
+__device__ __forceinline__ void gn_solve_store(const float (*red)[22], bool live, const float (&R)[9],
+                                               const float (&tv)[3], const float (&bs)[6], float csc, const Scales &sc,
+                                               float *st) {
+    const int lane = threadIdx.x & 63;
+    float H[15], g[5], r2 = 0.f, cnt = 0.f;
+#pragma unroll
+    for (int k = 0; k < 15; k++) H[k] = 0.f;
+#pragma unroll
+    for (int k = 0; k < 5; k++) g[k] = 0.f;
+    for (int q = 0; q < GNW; q++) {
+#pragma unroll
+        for (int k = 0; k < 15; k++) H[k] += red[q][k];
+#pragma unroll
+        for (int k = 0; k < 5; k++) g[k] += red[q][15 + k];
+        r2 += red[q][20];
+        cnt += red[q][21];
+    }
+    float d[5];
+    const bool ok = chol5_step(H, g, d) && live && cnt >= 5.f;
+    float dR[3][3];
+    rodrigues_f(d, dR);
+    float Rn[9], tn[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++)
+            Rn[i * 3 + j] = dR[i][0] * R[0 * 3 + j] + dR[i][1] * R[1 * 3 + j] + dR[i][2] * R[2 * 3 + j];
+#pragma unroll
+    for (int i = 0; i < 3; i++) tn[i] = tv[i] + d[3] * bs[i] + d[4] * bs[3 + i];
+    const float rn = __builtin_amdgcn_rsqf(tn[0] * tn[0] + tn[1] * tn[1] + tn[2] * tn[2]);
+    const float cs_new = fminf(sc.th_max, fmaxf(2.f * sqrtf(r2 / cnt), sc.th_min));
+    float dmax = 0.f;
+#pragma unroll
+    for (int i = 0; i < 5; i++) dmax = fmaxf(dmax, fabsf(d[i]));
+    // converged: a step below 1e-4 rad / unit-t (Gauss-Newton converges quadratically
+    // on exact data: the error left after such a step is ~1e-8) and a scale that moved
+    // < 2 % (noisy data: the pose then moves far below its noise floor); 1e-6 / 0.1 %
+    // measured the same on exact data and 9 % slower under 0.5 px noise
+    const bool done = dmax < 1e-4f && fabsf(cs_new - csc) <= 2e-2f * csc;
+    if (lane < 14) {  // lane k stores word k of the state (static register indexing)
+        float v = 0.f;
+#pragma unroll
+        for (int k = 0; k < 9; k++) v = lane == k ? Rn[k] : v;
+#pragma unroll
+        for (int k = 0; k < 3; k++) v = lane == 9 + k ? tn[k] * rn : v;
+        v = lane == 12 ? cs_new : v;
+        v = lane == 13 ? __int_as_float((ok ? 0 : 1) | (done ? 2 : 0)) : v;
+        st[lane] = v;
+    }
+}
+
+// ---- 5c. every thread of the group takes the accepted state ----
+__device__ __forceinline__ void gn_read_state(const float *st, float (&R)[9], float (&tv)[3], float (&bs)[6],
+                                              float &csc) {
+#pragma unroll
+    for (int i = 0; i < 9; i++) R[i] = st[i];
+#pragma unroll
+    for (int i = 0; i < 3; i++) tv[i] = st[9 + i];
+    tangent_basis_f(tv, bs);
+    csc = st[12];
+}
+
+// ---- 5. robust Gauss-Newton from (R, tv) at the Cauchy scale csc, in place: iteratively reweighted,
+//      Cauchy weights 1 / (1 + (r / c)^2) on the Sampson residuals below 3 thr (none above), the
+//      scale c_0 = csc, c_{k+1} = min(thr, max(2 rms_w, 0.01 thr)) (rms_w: the weighted rms of
+//      iteration k): on exact data c shrinks until the outliers that fell inside the band no longer
+//      pull (converges to machine precision), on noisy data it settles near 2 sigma.  Weights and
+//      Sampson denominators are frozen within an iteration.  The group's first wave solves the 5x5
+//      normal equations from the group's 22 sums; one block barrier per iteration after the sums,
+//      one after the state (both double-buffered). ----
+template <bool par>
+__device__ __forceinline__ void gauss_newton(int iters, const float4 *P, int n, const Scales &sc,
+                                             const Group<par> &g, PoseLds &s, float (&R)[9], float (&tv)[3],
+                                             float &csc) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    float bs[6];
+    tangent_basis_f(tv, bs);
+    bool act = true;  // this group still iterates (group-uniform)
+    for (int it = 0; it < iters; it++) {
+        float acc[22];
+        gn_accumulate(P, (!par || act) ? g.gt : n, n, g.G, R, tv, bs, __builtin_amdgcn_rcpf(csc), sc.r_cap, acc);
+        // the 22 sums reduced over the wave by recursive halving (a reduce-scatter), then
+        // the group's wave partials in LDS
+        float(*red)[22] = s.red[it & 1];
+        {
+            int vi;  // the sum this lane holds after the halving
+            const float f = gn_reduce_scatter22(acc, lane, vi);
+            if (vi >= 0) red[w][vi] = f;
+        }
+        __syncthreads();
+        float *st = s.state[it & 1][g.gid];
+        if (w == g.gw0) gn_solve_store<Group<par>::gnw>(red + g.gw0, !par || act, R, tv, bs, csc, sc, st);
+        __syncthreads();
+        const int flags = __float_as_int(st[13]);
+        if ((!par || act) && !(flags & 1)) gn_read_state(st, R, tv, bs, csc);
+        if constexpr (par) {
+            act = act && !(flags & 3);
+            // block-uniform exit: every group has stopped
+            const bool other = !(__float_as_int(s.state[it & 1][g.gid ^ 1][13]) & 3);
+            if (!act && !other) break;
+        } else {
+            if (flags & 3) break;  // the same decision in every thread
+        }
+    }
+}
+
+// ---- 6a. the robust cost of the refined pose (Cauchy at the scale thr, capped at 3 thr) and its
+//         inliers (Sampson distance < thr): the group's wave partials into s.fin / s.fin_n ----
+template <bool par>
+__device__ __forceinline__ void robust_cost(const float4 *P, int n, const Scales &sc, const Group<par> &g,
+                                            const float (&R)[9], const float (&tv)[3], PoseLds &s) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    float rcost = 0.f;
+    int ninl = 0;
+    for (int i = g.gt; i < n; i += g.G) {
+        float q[3], x2t[3], e, s2;
+        pose_sampson(R, tv, P[i], q, x2t, e, s2);
+        const float ar = s2 > 0.f ? fabsf(e) * __builtin_amdgcn_rsqf(s2) : sc.r_cap;
+        const float u = fminf(ar, sc.r_cap) / sc.th_max;
+        rcost += __logf(1.f + u * u);
+        ninl += ar < sc.th_max ? 1 : 0;
+    }
+    rcost = wave_sum(rcost);
+    ninl = wave_sum(ninl);
+    if (lane == 0) {
+        s.fin[w] = rcost;
+        s.fin_n[w] = ninl;
+    }
+}
+
+// ---- 6b. the lower robust cost over the starts wins (the same decision in every thread).
+//         Concurrent: each half's pose is read from candidate slot 0, start 0's group first, so a
+//         tie keeps start 0 as in the sequential schedule. ----
+template <bool par>
+__device__ __forceinline__ void keep_better(const float (&R)[9], const float (&tv)[3], const PoseLds &s,
+                                            Refined &best) {
+    for (int gg = 0; gg < (par ? 2 : 1); gg++) {
+        const int w0 = par ? 2 * gg : 0, nw = par ? 2 : 4;
+        float cost = 0.f;
+        int cn = 0;
+        for (int k = 0; k < nw; k++) {
+            cost += s.fin[w0 + k];
+            cn += s.fin_n[w0 + k];
+        }
+        if (cost < best.cost) {  // a tie keeps the earlier start
+            best.cost = cost;
+            best.inliers = cn;
+#pragma unroll
+            for (int i = 0; i < 9; i++) best.R[i] = par ? s.cand[gg][0][i] : R[i];
+#pragma unroll
+            for (int i = 0; i < 3; i++) best.t[i] = par ? s.cand[gg][0][9 + i] : tv[i];
+        }
+    }
+}
+
+template <bool par>
+__device__ __forceinline__ void refine_starts(const PoseArgs &a, const float4 *P, int n, PoseLds &s, Refined &best) {
+    const Group<par> g;
+    const Scales sc(a.thr2);
+    const int rounds = par ? 1 : s.nh;
+    for (int rd = 0; rd < rounds; rd++) {
+        float E[9];
+        for (int r = 0; r < 9; r++) E[r] = s.E[par ? g.gid : rd][r];
+        decompose_start(E, g, s);
+        const int bc = cheirality_vote(E, P, n, a.thr2, g, s);
+        float R[9], tv[3];
+#pragma unroll
+        for (int i = 0; i < 9; i++) R[i] = s.cand[g.gid][bc][i];
+#pragma unroll
+        for (int i = 0; i < 3; i++) tv[i] = s.cand[g.gid][bc][9 + i];
         // with refine_iters = 0 no Gauss-Newton barrier separates these reads of the start from
         // thread 0's write of the refined pose into candidate slot 0 below (concurrent schedule)
         if (a.refine_iters == 0) __syncthreads();
-        // the Cauchy scale.  An exact-fit start (s_exact: its inliers are exact projections)
+        // the Cauchy scale.  An exact-fit start (s.exact: its inliers are exact projections)
         // starts at the floor: the annealing from thr only lets the outliers inside the band stop
         // pulling, and at the floor they pull with weight ~(c / r)^2 from the first iteration --
         // one Gauss-Newton iteration instead of two on the headline's pairs, 7 % of the pose
         // (profiles/r06p_pose_iters.log)
-        float csc = (!par && rd == 0 && s_exact) ? th_min : th_max;
-        bool act = true;     // this group still iterates (group-uniform)
-        for (int it = 0; it < a.refine_iters; it++) {
-            float acc[22];  // sum w J^T J (15, upper), sum w J^T r (5), sum w r^2, sum w
+        float csc = (!par && rd == 0 && s.exact) ? sc.th_min : sc.th_max;
+        gauss_newton(a.refine_iters, P, n, sc, g, s, R, tv, csc);
+        robust_cost(P, n, sc, g, R, tv, s);
+        if (par && g.gt == 0) {  // each half's refined pose, for the threads that write the output
 #pragma unroll
-            for (int k = 0; k < 22; k++) acc[k] = 0.f;
-            const float rcs = __builtin_amdgcn_rcpf(csc);
-            for (int i = (!par || act) ? gt : n; i < n; i += G) {
-                const float4 p = P[i];
-                const float x1[3] = {p.x, p.y, 1.f}, x2[3] = {p.z, p.w, 1.f};
-                const float q[3] = {R[0] * x1[0] + R[1] * x1[1] + R[2], R[3] * x1[0] + R[4] * x1[1] + R[5],
-                                    R[6] * x1[0] + R[7] * x1[1] + R[8]};
-                // e = x2^T [t]x R x1 = (x2 x t) . (R x1)
-                const float x2t[3] = {x2[1] * tv[2] - x2[2] * tv[1], x2[2] * tv[0] - x2[0] * tv[2],
-                                      x2[0] * tv[1] - x2[1] * tv[0]};
-                const float e = x2t[0] * q[0] + x2t[1] * q[1] + x2t[2] * q[2];
-                const float Ex1[2] = {tv[1] * q[2] - tv[2] * q[1], tv[2] * q[0] - tv[0] * q[2]};  // (E x1)_{0,1}
-                float Etx2[2];  // (E^T x2)_{0,1} = (R^T (x2 x t))_{0,1}
+            for (int i = 0; i < 9; i++) s.cand[g.gid][0][i] = R[i];
 #pragma unroll
-                for (int c = 0; c < 2; c++) Etx2[c] = R[c] * x2t[0] + R[3 + c] * x2t[1] + R[6 + c] * x2t[2];
-                const float s2 = Ex1[0] * Ex1[0] + Ex1[1] * Ex1[1] + Etx2[0] * Etx2[0] + Etx2[1] * Etx2[1];
-                if (!(s2 > 0.f)) continue;
-                const float inv = __builtin_amdgcn_rsqf(s2);  // native: a GN weight, not an output
-                const float r = e * inv;                      // Sampson distance
-                if (!(fabsf(r) < r_cap)) continue;
-                const float u = r * rcs;
-                const float wt = __builtin_amdgcn_rcpf(1.f + u * u);
-                // d e / d omega = q x (x2 x t)  (R <- exp(omega) R);  d e / d t = q x x2
-                const float dw[3] = {q[1] * x2t[2] - q[2] * x2t[1], q[2] * x2t[0] - q[0] * x2t[2],
-                                     q[0] * x2t[1] - q[1] * x2t[0]};
-                const float dt[3] = {q[1] * x2[2] - q[2] * x2[1], q[2] * x2[0] - q[0] * x2[2],
-                                     q[0] * x2[1] - q[1] * x2[0]};
-                const float J[5] = {dw[0] * inv, dw[1] * inv, dw[2] * inv,
-                                    (dt[0] * bs[0] + dt[1] * bs[1] + dt[2] * bs[2]) * inv,
-                                    (dt[0] * bs[3] + dt[1] * bs[4] + dt[2] * bs[5]) * inv};
-                float Jw[5];
-#pragma unroll
-                for (int v = 0; v < 5; v++) Jw[v] = J[v] * wt;
-                int k = 0;
-#pragma unroll
-                for (int v = 0; v < 5; v++) {
-#pragma unroll
-                    for (int x = v; x < 5; x++) acc[k++] += Jw[v] * J[x];
-                }
-#pragma unroll
-                for (int v = 0; v < 5; v++) acc[15 + v] += Jw[v] * r;
-                acc[20] += wt * r * r;
-                acc[21] += wt;
-            }
-            // the 22 sums reduced over the wave by recursive halving (a reduce-scatter), then
-            // the group's wave partials in LDS
-            float(*red)[22] = s_red[it & 1];
-            {
-                int vi;  // the sum this lane holds after the halving
-                const float f = gn_reduce_scatter22(acc, lane, vi);
-                if (vi >= 0) red[w][vi] = f;
-            }
-            __syncthreads();
-            float *st = s_state[it & 1][gid];
-            if (w == gw0) {
-                float H[15], g[5], r2 = 0.f, cnt = 0.f;
-#pragma unroll
-                for (int k = 0; k < 15; k++) H[k] = 0.f;
-#pragma unroll
-                for (int k = 0; k < 5; k++) g[k] = 0.f;
-                for (int q = 0; q < gnw; q++) {
-#pragma unroll
-                    for (int k = 0; k < 15; k++) H[k] += red[gw0 + q][k];
-#pragma unroll
-                    for (int k = 0; k < 5; k++) g[k] += red[gw0 + q][15 + k];
-                    r2 += red[gw0 + q][20];
-                    cnt += red[gw0 + q][21];
-                }
-                // float Cholesky on the native reciprocal square root (the step only has to be
-                // a descent direction); every loop fully unrolled: static register indexing
-                float A[5][5];
-#pragma unroll
-                for (int v = 0, k = 0; v < 5; v++)
-#pragma unroll
-                    for (int x = v; x < 5; x++, k++) {
-                        A[v][x] = H[k];
-                        A[x][v] = H[k];
-                    }
-#pragma unroll
-                for (int v = 0; v < 5; v++) A[v][v] = A[v][v] * (1.0f + 1e-6f) + 1e-30f;
-                float L[5][5] = {}, rl[5] = {};
-                bool ok = (!par || act) && cnt >= 5.f;
-#pragma unroll
-                for (int i = 0; i < 5; i++)
-#pragma unroll
-                    for (int j = 0; j <= i; j++) {
-                        float sum = A[i][j];
-#pragma unroll
-                        for (int m = 0; m < j; m++) sum -= L[i][m] * L[j][m];
-                        if (i == j) {
-                            ok = ok && sum > 0.f;
-                            rl[i] = __builtin_amdgcn_rsqf(fmaxf(sum, 1e-30f));  // 1 / L[i][i]
-                            L[i][i] = fmaxf(sum, 1e-30f) * rl[i];
-                        } else {
-                            L[i][j] = sum * rl[j];
-                        }
-                    }
-                float y[5], d[5];
-#pragma unroll
-                for (int i = 0; i < 5; i++) {
-                    float sum = -g[i];
-#pragma unroll
-                    for (int m = 0; m < i; m++) sum -= L[i][m] * y[m];
-                    y[i] = sum * rl[i];
-                }
-#pragma unroll
-                for (int i = 4; i >= 0; i--) {
-                    float sum = y[i];
-#pragma unroll
-                    for (int m = i + 1; m < 5; m++) sum -= L[m][i] * d[m];
-                    d[i] = sum * rl[i];
-                }
-                float dR[3][3];
-                rodrigues_f(d, dR);
-                float Rn[9], tn[3];
-#pragma unroll
-                for (int i = 0; i < 3; i++)
-#pragma unroll
-                    for (int j = 0; j < 3; j++)
-                        Rn[i * 3 + j] = dR[i][0] * R[0 * 3 + j] + dR[i][1] * R[1 * 3 + j] + dR[i][2] * R[2 * 3 + j];
-#pragma unroll
-                for (int i = 0; i < 3; i++) tn[i] = tv[i] + d[3] * bs[i] + d[4] * bs[3 + i];
-                const float rn = __builtin_amdgcn_rsqf(tn[0] * tn[0] + tn[1] * tn[1] + tn[2] * tn[2]);
-                const float cs_new = fminf(th_max, fmaxf(2.f * sqrtf(r2 / cnt), th_min));
-                float dmax = 0.f;
-#pragma unroll
-                for (int i = 0; i < 5; i++) dmax = fmaxf(dmax, fabsf(d[i]));
-                // converged: a step below 1e-4 rad / unit-t (Gauss-Newton converges quadratically
-                // on exact data: the error left after such a step is ~1e-8) and a scale that moved
-                // < 2 % (noisy data: the pose then moves far below its noise floor); 1e-6 / 0.1 %
-                // measured the same on exact data and 9 % slower under 0.5 px noise
-                const bool done = dmax < 1e-4f && fabsf(cs_new - csc) <= 2e-2f * csc;
-                // lane k < 14 stores word k of the state (static register indexing):
-                // R (9), t (3), scale, flags (bit 0: failed or stopped -- keep the old state;
-                // bit 1: converged)
-                if (lane < 14) {
-                    float v = 0.f;
-#pragma unroll
-                    for (int k = 0; k < 9; k++) v = lane == k ? Rn[k] : v;
-#pragma unroll
-                    for (int k = 0; k < 3; k++) v = lane == 9 + k ? tn[k] * rn : v;
-                    v = lane == 12 ? cs_new : v;
-                    v = lane == 13 ? __int_as_float((ok ? 0 : 1) | (done ? 2 : 0)) : v;
-                    st[lane] = v;
-                }
-            }
-            __syncthreads();
-            const int flags = __float_as_int(st[13]);
-            if ((!par || act) && !(flags & 1)) {
-#pragma unroll
-                for (int i = 0; i < 9; i++) R[i] = st[i];
-#pragma unroll
-                for (int i = 0; i < 3; i++) tv[i] = st[9 + i];
-                tangent_basis_f(tv, bs);
-                csc = st[12];
-            }
-            if constexpr (par) {
-                act = act && !(flags & 3);
-                // block-uniform exit: every group has stopped
-                const bool other = !(__float_as_int(s_state[it & 1][gid ^ 1][13]) & 3);
-                if (!act && !other) break;
-            } else {
-                if (flags & 3) break;  // the same decision in every thread
-            }
-        }
-
-        // ---- the robust cost of the refined pose (Cauchy at the scale thr, capped at 3 thr) and
-        //      its inliers (Sampson distance < thr): the lower cost over the starts wins ----
-        float rcost = 0.f;
-        int ninl = 0;
-        for (int i = gt; i < n; i += G) {
-            const float4 p = P[i];
-            const float q[3] = {R[0] * p.x + R[1] * p.y + R[2], R[3] * p.x + R[4] * p.y + R[5],
-                                R[6] * p.x + R[7] * p.y + R[8]};
-            const float x2t[3] = {p.w * tv[2] - tv[1], tv[0] - p.z * tv[2], p.z * tv[1] - p.w * tv[0]};
-            const float e = x2t[0] * q[0] + x2t[1] * q[1] + x2t[2] * q[2];
-            const float Ex1[2] = {tv[1] * q[2] - tv[2] * q[1], tv[2] * q[0] - tv[0] * q[2]};
-            float Etx2[2];
-#pragma unroll
-            for (int c = 0; c < 2; c++) Etx2[c] = R[c] * x2t[0] + R[3 + c] * x2t[1] + R[6 + c] * x2t[2];
-            const float s2 = Ex1[0] * Ex1[0] + Ex1[1] * Ex1[1] + Etx2[0] * Etx2[0] + Etx2[1] * Etx2[1];
-            const float ar = s2 > 0.f ? fabsf(e) * __builtin_amdgcn_rsqf(s2) : r_cap;
-            const float u = fminf(ar, r_cap) / th_max;
-            rcost += __logf(1.f + u * u);
-            ninl += ar < th_max ? 1 : 0;
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            rcost += __shfl_xor(rcost, o, 64);
-            ninl += __shfl_xor(ninl, o, 64);
-        }
-        if (lane == 0) {
-            s_fin[w] = rcost;
-            s_fin_n[w] = ninl;
-        }
-        if (par && gt == 0) {  // each half's refined pose, for the threads that write the output
-#pragma unroll
-            for (int i = 0; i < 9; i++) s_cand[gid][0][i] = R[i];
-#pragma unroll
-            for (int i = 0; i < 3; i++) s_cand[gid][0][9 + i] = tv[i];
+            for (int i = 0; i < 3; i++) s.cand[g.gid][0][9 + i] = tv[i];
         }
         __syncthreads();
-        // the group costs; concurrent: start 0's group first, so a tie keeps start 0 as in the
-        // sequential schedule
-        for (int gg = 0; gg < (par ? 2 : 1); gg++) {
-            const int w0 = par ? 2 * gg : 0, nw = par ? 2 : 4;
-            float cost = 0.f;
-            int cn_ = 0;
-            for (int k = 0; k < nw; k++) {
-                cost += s_fin[w0 + k];
-                cn_ += s_fin_n[w0 + k];
-            }
-            if (cost < bcost) {  // the same decision in every thread (a tie keeps the earlier start)
-                bcost = cost;
-                bn = cn_;
-#pragma unroll
-                for (int i = 0; i < 9; i++) bR[i] = par ? s_cand[gg][0][i] : R[i];
-#pragma unroll
-                for (int i = 0; i < 3; i++) bT[i] = par ? s_cand[gg][0][9 + i] : tv[i];
-            }
-        }
-        __syncthreads();  // s_uv, s_cand, s_votes, s_fin are the next start's
+        keep_better<par>(R, tv, s, best);
+        __syncthreads();  // s.uv, s.cand, s.votes, s.fin are the next start's
         if constexpr (!par)
-            if (csc <= th_min * 1.0001f) break;  // an exact fit: no second start needed
+            if (csc <= sc.th_min * 1.0001f) break;  // an exact fit: no second start needed
     }
-    };
-    if (s_nh == 2 && !s_exact)
-        refine(std::true_type{});
+}
+
+__global__ __launch_bounds__(NT, PE_WAVES) void k_pose_ransac(PoseArgs a, const int *__restrict__ nv,
+                                                    const float *__restrict__ pts0,
+                                                    const float *__restrict__ pts1,
+                                                    const int *__restrict__ match_idx,
+                                                    const float *__restrict__ kp1, float *__restrict__ T,
+                                                    int *__restrict__ num_matches, int *__restrict__ num_inliers,
+                                                    int *__restrict__ status) {
+    extern __shared__ __attribute__((aligned(16))) float4 P[];  // [min(cap, MAXP)]
+    __shared__ PoseLds s;
+    const int b = blockIdx.x, t = threadIdx.x;
+    const PoseOut out{T, num_matches, num_inliers, status};
+    int n_all;
+    const int n = gather_pairs(a, b, min(max(nv[b], 0), a.cap), pts0, pts1, match_idx, kp1, P, s.wsum, &n_all);
+    if (n < 8) return out.write_none(b, n_all, n_all == 0 ? MV_ERR_NO_POINTS : MV_ERR_DEGENERATE);
+    Hyp hyp;
+    score_hypotheses(a, b, P, n, s, hyp);
+    keep_wave_survivors(hyp, s);
+    __syncthreads();
+    rescore_survivors(a, P, n, s);
+    __syncthreads();
+    if (t == 0) pick_starts(a, n, s);
+    __syncthreads();
+    if (s.nh == 0) return out.write_none(b, n_all, MV_ERR_DEGENERATE);
+    Refined best;
+    if (s.nh == 2 && !s.exact)
+        refine_starts<true>(a, P, n, s, best);
     else
-        refine(std::false_type{});
-    {  // [R | t] row-major, thread t < 12 writes entry t (static register indexing)
-        float v = 0.f;
+        refine_starts<false>(a, P, n, s, best);
+    // [R | t] row-major, thread t < 12 writes entry t (static register indexing)
+    float v = 0.f;
 #pragma unroll
-        for (int k = 0; k < 12; k++) v = t == k ? (k % 4 < 3 ? bR[(k / 4) * 3 + k % 4] : bT[k / 4]) : v;
-        if (t < 12) To[t] = v;
-    }
-    if (t == 0) {
-        num_inliers[b] = bn;
-        if (num_matches) num_matches[b] = n_all;
-        status[b] = MV_OK;
-    }
+    for (int k = 0; k < 12; k++) v = t == k ? (k % 4 < 3 ? best.R[(k / 4) * 3 + k % 4] : best.t[k / 4]) : v;
+    out.write(b, v, n_all, best.inliers, MV_OK);
 }
 
 }  // namespace
 
 namespace mv {
 
-size_t intended_pose_scratch_bytes(int batch, int cap) {
-    (void)batch;
-    (void)cap;
-    return 256;
-}
-
-int launch_intended_pose(hipStream_t s, void *scratch, const mv_pose_params *p, int batch, int cap, const int *n,
-                         const float *pts0, const float *pts1, const int *match_idx, const float *kp1, float *T,
-                         int *num_matches, int *num_inliers, int *status) {
-    (void)scratch;
+int launch_intended_pose(hipStream_t s, const mv_pose_params *p, int batch, int cap, const int *n, const float *pts0,
+                         const float *pts1, const int *match_idx, const float *kp1, float *T, int *num_matches,
+                         int *num_inliers, int *status) {
     MV_REQUIRE(p->hypotheses > 0 && p->fx > 0 && p->fy > 0 && p->refine_iters >= 0);
     PoseArgs a;
     a.cap = cap;

@@ -199,10 +199,8 @@ int mv_pose_batch_dev(mv_context *ctx, const mv_pose_params *p, int batch, int c
                       const float *pts1, float *T, int *num_inliers, int *status) {
     MV_REQUIRE(ctx != nullptr);
     MV_HIP_TRY(hipSetDevice(ctx->device));
-    void *scr = mv::scratch(ctx, mv::pose_scratch_bytes(batch, cap));
-    if (!scr) return MV_ERR_OUT_OF_MEMORY;
-    return mv::launch_pose(ctx->stream, scr, p, batch, cap, n, pts0, pts1, nullptr, nullptr, T, nullptr,
-                           num_inliers, status);
+    return mv::launch_pose(ctx->stream, p, batch, cap, n, pts0, pts1, nullptr, nullptr, T, nullptr, num_inliers,
+                           status);
 }
 
 int mv_pose_from_matches_dev(mv_context *ctx, const mv_pose_params *p, int batch, int cap, const int *n0,
@@ -210,10 +208,8 @@ int mv_pose_from_matches_dev(mv_context *ctx, const mv_pose_params *p, int batch
                              int *num_inliers, int *status) {
     MV_REQUIRE(ctx != nullptr && match_idx != nullptr);
     MV_HIP_TRY(hipSetDevice(ctx->device));
-    void *scr = mv::scratch(ctx, mv::pose_scratch_bytes(batch, cap));
-    if (!scr) return MV_ERR_OUT_OF_MEMORY;
-    return mv::launch_pose(ctx->stream, scr, p, batch, cap, n0, kp0, nullptr, match_idx, kp1, T, num_matches,
-                           num_inliers, status);
+    return mv::launch_pose(ctx->stream, p, batch, cap, n0, kp0, nullptr, match_idx, kp1, T, num_matches, num_inliers,
+                           status);
 }
 
 int mv_ransac_stub_host(mv_context *ctx, int n, const float *pts1, const float *pts2, float thresh, float *best_E,
@@ -327,11 +323,7 @@ int mv_track_pair_host(mv_context *ctx, const mv_track_params *p, int rows, int 
     if (!st)
         st = mv_window_match_batch_dev(ctx, &p->window, 1, rows, cols, d_d0, d_mi0, d_pr0, d_d1, N, d_ns, d_pa,
                                        d_ix, d_nm, d_p1, d_p2, nullptr);
-    if (!st) {
-        void *scr = mv::scratch(ctx, mv::pose_scratch_bytes(1, M));
-        if (!scr) return MV_ERR_OUT_OF_MEMORY;
-        st = mv::launch_pose(s, scr, &p->pose, 1, M, d_nm, d_p1, d_p2, nullptr, nullptr, d_T, nullptr, d_ni, d_ps);
-    }
+    if (!st) st = mv::launch_pose(s, &p->pose, 1, M, d_nm, d_p1, d_p2, nullptr, nullptr, d_T, nullptr, d_ni, d_ps);
     if (st) return st;
     int nm = 0, tst = 0, pst = 0;
     MV_HIP_TRY(hipMemcpyAsync(&nm, d_nm, 4, hipMemcpyDeviceToHost, s));

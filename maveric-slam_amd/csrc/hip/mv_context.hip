@@ -291,11 +291,7 @@ int mv_context_reserve(mv_context *ctx, int batch, int cap) {
     }
     const int st2 = mv::grow(ctx, ctx->ap_image2, img, "all-pairs scratch");  // run_prepare's second image
     if (st2 != MV_OK) return st2;
-    size_t need = mv::allpairs_i8_scratch_bytes(batch, cap);
-    size_t b;
-    b = mv::pose_scratch_bytes(batch, cap);
-    if (b > need) need = b;
-    if (!mv::scratch(ctx, need)) return MV_ERR_OUT_OF_MEMORY;
+    if (!mv::scratch(ctx, mv::allpairs_i8_scratch_bytes(batch, cap))) return MV_ERR_OUT_OF_MEMORY;
     return MV_OK;
 }
 

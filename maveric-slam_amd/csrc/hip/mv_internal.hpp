@@ -191,10 +191,13 @@ size_t allpairs_i8_scratch_bytes(int batch, int cap);
 int launch_allpairs_i8(hipStream_t s, void *scratch, int batch, int cap, const int *n0, const int *n1,
                        const int8_t *desc0, const int8_t *desc1, int *match_idx, int *match_dot, bool direct = false,
                        int *count_host = nullptr);
-size_t pose_scratch_bytes(int batch, int cap);
-int launch_pose(hipStream_t s, void *scratch, const mv_pose_params *p, int batch, int cap, const int *n,
-                const float *pts0, const float *pts1, const int *match_idx, const float *kp1, float *T,
-                int *num_matches, int *num_inliers, int *status);
+// the batched pose by p->semantics (k_pose.hip); as-intended: k_pose_ransac (k_pose_intended.hip)
+int launch_pose(hipStream_t s, const mv_pose_params *p, int batch, int cap, const int *n, const float *pts0,
+                const float *pts1, const int *match_idx, const float *kp1, float *T, int *num_matches,
+                int *num_inliers, int *status);
+int launch_intended_pose(hipStream_t s, const mv_pose_params *p, int batch, int cap, const int *n, const float *pts0,
+                         const float *pts1, const int *match_idx, const float *kp1, float *T, int *num_matches,
+                         int *num_inliers, int *status);
 int launch_ransac_stub(hipStream_t s, int n, const float *pts1, const float *pts2, float thresh, float *E,
                        int *inliers, int *num_inliers);
 int launch_recover_pose(hipStream_t s, const float *E, float *R1, float *R2, float *t);

@@ -1,7 +1,8 @@
 // mv_wave.hpp -- wave-level device helpers shared by the MFMA sweep kernels (k_allpairs_f32,
 // k_allpairs_i8, k_allpairs_q8 / k_allpairs_direct through q8_common.hpp, k_frontend): the MFMA
 // operand vector types, the LDS-DMA issue forms with their counted wait, the tagged top-2 fold,
-// the ds_swizzle xor-shuffles and the XCD block remap.  One definition of each.
+// the ds_swizzle xor-shuffles and the XCD block remap -- and by the pose and front-end kernels: the
+// wave sum / arg-min key / scan by shuffles and the block scan.  One definition of each.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -103,6 +104,52 @@ template <int M>
 __device__ __forceinline__ int swz_xor(int v) {
     static_assert(M >= 0 && M < 32, "ds_swizzle bit mode stays within 32 lanes");
     return __builtin_amdgcn_ds_swizzle(v, (M << 10) | 0x1F);
+}
+
+// wave64 butterfly reductions by __shfl_xor: every lane ends with the result
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long k) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long k2 = __shfl_xor(k, o, 64);
+        k = k2 < k ? k2 : k;
+    }
+    return k;
+}
+
+// inclusive scan over the wave's lanes
+__device__ __forceinline__ int wave_scan_incl(int x) {
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int y = __shfl_up(x, o, 64);
+        if (lane >= o) x += y;
+    }
+    return x;
+}
+
+// Exclusive scan of v over the block's NT threads (thread order), *total = the block sum; wsum:
+// NT / 64 ints of LDS, free again on return (three barriers).
+template <int NT>
+__device__ __forceinline__ int block_scan_excl(int v, int *total, int *wsum) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int x = wave_scan_incl(v);
+    if (lane == 63) wsum[w] = x;
+    __syncthreads();
+    if (w == 0) {
+        const int s = wave_scan_incl(lane < NT / 64 ? wsum[lane] : 0);
+        if (lane < NT / 64) wsum[lane] = s;  // inclusive wave prefix
+    }
+    __syncthreads();
+    const int off = (w > 0 ? wsum[w - 1] : 0) + x - v;
+    *total = wsum[NT / 64 - 1];
+    __syncthreads();
+    return off;
 }
 
 }  // namespace wave

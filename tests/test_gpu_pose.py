@@ -4,6 +4,8 @@
   transforms (outputs/transform_*.npy, via synthetic projections with the K of
   pairwise_pnp.py:667-669) within the north-star tolerance 1e-4."""
 import ctypes
+import os
+import sys
 
 import numpy as np
 import pytest
@@ -95,6 +97,32 @@ def _pose_batch(ctx, torch, params, P0, P1, n):
     torch.cuda.synchronize()
     ctx.set_stream(None)
     return T.cpu().numpy(), ni.cpu().numpy(), st.cpu().numpy()
+
+
+def _pose_from_matches(ctx, torch, params, n0, idx, kp0, kp1):
+    dev = torch.device("cuda:0")
+    B = idx.shape[0]
+    T = torch.zeros((B, 3, 4), dtype=torch.float32, device=dev)
+    nm, ni, st = (torch.full((B,), 99, dtype=torch.int32, device=dev) for _ in range(3))
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+    ctx.set_stream(torch.cuda.current_stream())
+    ctx.pose_from_matches(params, t(n0), t(idx), t(kp0), t(kp1), T, nm, ni, st)
+    torch.cuda.synchronize()
+    ctx.set_stream(None)
+    return T.cpu().numpy(), nm.cpu().numpy(), ni.cpu().numpy(), st.cpu().numpy()
+
+
+def _kitti_params(**kw):
+    import mvtrack
+
+    K = synth.KITTI_K
+    return mvtrack.pose_params(mvtrack.AS_INTENDED, fx=K[0, 0], fy=K[1, 1], cx=K[0, 2], cy=K[1, 2], **kw)
+
+
+def _padded(P, cap):
+    out = np.zeros((P.shape[0], cap, 2), np.float32)
+    out[:, :P.shape[1]] = P
+    return out
 
 
 def pose_error(T, Rg, tg):
@@ -238,3 +266,75 @@ def test_pose_clamps_counts_and_match_indices(ctx, torch_cuda, semantics):
     assert (a[1] == (good >= 0).sum(1)).all()
     for x, y in zip(a, b):
         assert (np.ascontiguousarray(x).view(np.int32) == np.ascontiguousarray(y).view(np.int32)).all()
+
+
+def _ab():
+    tools = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools")
+    if tools not in sys.path:
+        sys.path.insert(0, tools)
+    import ab_pose_bits  # the data builders of the A/B tool: scene(), as_matches()
+
+    return ab_pose_bits
+
+
+def test_intended_pose_gather_paths_agree(ctx, torch_cuda):
+    """The same 300 exact correspondences (30 % outliers) per pair at cap 1100, as explicit pairs
+    (n = 300: at most 4 entries per thread, the gather prefetched ahead of the scan) and as a match
+    over all 1100 rows of frame 0 (5 entries per thread: the loop gather; the 300 matched rows in the
+    same order, frame 1 permuted, every other row -1): bit-identical poses."""
+    ab = _ab()
+    Ts = load_golden("poses.npz")["transforms_785_790"][:2]
+    B, n, cap = 2, 300, 1100
+    P0, P1 = ab.scene(Ts, n, 0, 0.3, 5)
+    kp0, kp1, idx = ab.as_matches(P0, P1, cap, 3)
+    assert ((idx >= 0).sum(1) == n).all() and not (idx[idx >= 0] == np.nonzero(idx >= 0)[1]).all()
+    prm = _kitti_params(hypotheses=256)
+    Ta, nia, sta = _pose_batch(ctx, torch_cuda, prm, _padded(P0, cap), _padded(P1, cap), np.full(B, n, np.int32))
+    Tb, nmb, nib, stb = _pose_from_matches(ctx, torch_cuda, prm, np.full(B, cap, np.int32), idx, kp0, kp1)
+    assert (bits(Ta) == bits(Tb)).all() and (nia == nib).all() and (sta == stb).all()
+    assert (nmb == n).all() and (sta == 0).all()
+    for b, Tg in enumerate(Ts):
+        eR, et = pose_error(Ta[b], Tg[:, :3], Tg[:, 3])
+        assert eR < TOL and et < TOL, (b, eR, et)
+
+
+def test_intended_pose_keeps_first_4096_correspondences(ctx, torch_cuda):
+    """More correspondences than the kernel holds in LDS (4096): n = 4200 gives the pose of the
+    first 4096 in query order, bit for bit, through both entry points; num_matches still counts all."""
+    ab = _ab()
+    Ts = load_golden("poses.npz")["transforms_785_790"][:1]
+    cap = 4200
+    P0, P1 = ab.scene(Ts, cap, 0, 0.2, 6)
+    prm = _kitti_params(hypotheses=256)
+    kp0, kp1, idx = ab.as_matches(P0, P1, cap, 4)  # every row matched, frame 1 permuted
+    res = []  # (T, num_inliers, status) of n = 4200 and n = 4096, explicit pairs then matches
+    for n in (cap, 4096):
+        res.append(_pose_batch(ctx, torch_cuda, prm, P0, P1, np.array([n], np.int32)))
+    for n in (cap, 4096):
+        T, nm, ni, st = _pose_from_matches(ctx, torch_cuda, prm, np.array([n], np.int32), idx, kp0, kp1)
+        assert nm[0] == n
+        res.append((T, ni, st))
+    assert res[0][2][0] == 0 and res[0][1][0] >= 0.7 * 4096
+    for T, ni, st in res[1:]:
+        assert (bits(T) == bits(res[0][0])).all() and (ni == res[0][1]).all() and (st == res[0][2]).all()
+
+
+def test_intended_pose_without_refinement_both_schedules(ctx, torch_cuda):
+    """refine_iters = 0 on an exact pair (sequential schedule) and a 1 px-noise pair (concurrent
+    schedule: only its extra barrier orders the reads of the start against the write of the
+    result) in one batch: deterministic, finite, and the exact pair's pose does not depend on its
+    neighbour."""
+    ab = _ab()
+    Ts = load_golden("poses.npz")["transforms_785_790"][:1]
+    n = 400
+    e0, e1 = ab.scene(Ts, n, 0, 0.3, 7)
+    z0, z1 = ab.scene(Ts, n, 1.0, 0.3, 8)
+    P0, P1 = np.concatenate([e0, z0]), np.concatenate([e1, z1])
+    prm = _kitti_params(hypotheses=512, inlier_thresh=2.0, refine_iters=0, seed=9)
+    r1 = _pose_batch(ctx, torch_cuda, prm, P0, P1, np.full(2, n, np.int32))
+    r2 = _pose_batch(ctx, torch_cuda, prm, P0, P1, np.full(2, n, np.int32))
+    alone = _pose_batch(ctx, torch_cuda, prm, P0[:1], P1[:1], np.full(1, n, np.int32))
+    for x, y in zip(r1, r2):
+        assert (bits(x) == bits(y)).all() if x.dtype == np.float32 else (x == y).all()
+    assert (r1[2] == 0).all() and np.isfinite(r1[0]).all() and (r1[1] >= 8).all()
+    assert (bits(r1[0][0]) == bits(alone[0][0])).all() and r1[1][0] == alone[1][0]
