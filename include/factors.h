@@ -39,8 +39,14 @@ int mv_pose_normal_equations_dev(mv_context *ctx, int num_poses, const int *pose
  * MV_AS_BUILT (the reference's index, local_bundle_adjustment.c:158) and i * num_poses + p
  * with MV_AS_INTENDED.  C [batch][S][S] (S = 6 num_poses + 1, column-major) is accumulated
  * in place: the pose-pose Schur complement (plus the reference's residual row).  The
- * reference's order throughout (bit-identical to its own functions).  LDS: 4 (100 + 9 chunk^2
- * + 6 S chunk + S^2) bytes <= 64 KiB. */
+ * reference's order throughout (bit-identical to its own functions).
+ * A ragged last chunk (num_ldmks % chunk != 0): with MV_AS_INTENDED it holds only the
+ * landmarks that exist -- only their factors are read (the rest of the chunk's J entries may
+ * hold anything, NaN included), only their 3 x 3 blocks are inverted, and the padded blocks
+ * stay zero, so C is the Schur complement over exactly num_ldmks landmarks.  With MV_AS_BUILT
+ * every chunk walks `chunk` landmarks, as the reference's loop does (:128).
+ * LDS: 4 (100 + 9 chunk^2 + 6 S chunk + S^2) bytes <= 64 KiB, else MV_ERR_INVALID_ARG with C
+ * untouched. */
 int mv_lba_schur_dev(mv_context *ctx, int batch, int num_poses, int num_ldmks, int chunk, int semantics,
                      const float *J, float *C);
 

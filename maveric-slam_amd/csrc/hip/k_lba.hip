@@ -8,6 +8,9 @@
 //   (3) invert A's 3x3 blocks (cofactor formulas, invert_3x3);
 //   (4) BA = A B   (matmul2: 0 * old BA, then sequential k);
 //   (5) C = C - B^T BA over the pose block (matmul2 with -1 scale, sequential k).
+// A ragged last chunk (L % LC != 0): as built it walks LC landmarks like every other chunk (the
+// reference's loop); as intended (2) and (3) stop at the landmarks that exist, so the padded
+// blocks of A stay zero, the padded J entries are never read, and (4)/(5) add exact zeros.
 // Every value sees the reference's operations in its order, so C is bit-identical to the
 // sequential loop (oracle/mv_oracle.c orc_lba_schur, itself pinned to the reference's own
 // functions).  Latency-bound by the chunk sequence (the Schur accumulation is sequential);
@@ -38,6 +41,7 @@ __global__ __launch_bounds__(256) void k_lba_schur(int P, int L, int LC, int as_
     for (int i = t; i < S * TL; i += 256) BA[i] = 0.f;
     __syncthreads();
     for (int ch = 0; ch < nch; ch++) {
+        const int nl = as_built ? LC : min(LC, L - ch * LC);  // landmarks of this chunk
         // (1)
         for (int i = t; i < TL * 3; i += 256) {  // diagonal blocks: row I + r, col I + c
             const int blk = i / 9, r = (i % 9) / 3, c = i % 3, I = 3 * blk;
@@ -48,7 +52,7 @@ __global__ __launch_bounds__(256) void k_lba_schur(int P, int L, int LC, int as_
         // (2)
         if (t < 64) {
             const float *Jc = Jb + (long)ch * P * LC * 20;
-            for (int ci = 0; ci < LC; ci++)
+            for (int ci = 0; ci < nl; ci++)
                 for (int p = 0; p < P; p++) {
                     const int pi = p * 6, li = ci * 3;
                     const float *Jf = Jc + 20 * (as_built ? p * ci : ci * P + p);
@@ -91,7 +95,7 @@ __global__ __launch_bounds__(256) void k_lba_schur(int P, int L, int LC, int as_
         }
         __syncthreads();
         // (3) invert_3x3 of each diagonal block (column-major copy, cofactors / det)
-        if (t < LC) {
+        if (t < nl) {
             float *m = A + (3 * t) * TL + 3 * t;
             float a[9], v[9];
             for (int j = 0; j < 3; j++)

@@ -1047,7 +1047,10 @@ ORC_EXPORT void orc_lba_schur(int P, int L, int LC, int as_built, const float *J
                 for (int j = 0; j < 3; j++) A[(I + i) * TL + I + j] = 0;
         memset(Bc, 0, sizeof(float) * (size_t)S * TL);
         const float *Jc = J + (size_t)ch * P * LC * 20;
-        for (int ci = 0; ci < LC; ci++)
+        /* a ragged last chunk: as built walks LC landmarks (main's loop); as intended only those
+         * that exist -- the padded blocks of A stay zero and the padded J is never read */
+        const int nl = as_built || L - c0 > LC ? LC : L - c0;
+        for (int ci = 0; ci < nl; ci++)
             for (int p = 0; p < P; p++) {
                 const int pi = p * 6, li = ci * 3;
                 const float *Jf = Jc + 20 * (size_t)(as_built ? p * ci : ci * P + p);
@@ -1058,7 +1061,7 @@ ORC_EXPORT void orc_lba_schur(int P, int L, int LC, int as_built, const float *J
                 orc_madd(H + 33, C + pi * (S + 1), 6, 6, 10, S);
                 orc_madd(H + 39, C + (pi + 1) * S - 1, 1, 6, 10, S);
             }
-        for (int I = 0; I < TL; I += 3) orc_inv3(A + I * TL + I, TL);
+        for (int I = 0; I < 3 * nl; I += 3) orc_inv3(A + I * TL + I, TL);
         orc_mm2(TL, 6 * P, TL, A, Bc, BA, TL, S, S, 1.f, 1.f, 0.f, 0, 0);
         orc_mm2(6 * P, 6 * P, TL, Bc, BA, C, S, S, S, -1.f, 1.f, 1.f, 1, 0);
     }

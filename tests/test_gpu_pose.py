@@ -36,6 +36,20 @@ def test_svd3_and_recover_pose_vs_oracle(ctx, orc):
         assert (bits(R1) == bits(a)).all() and (bits(R2) == bits(b)).all() and (bits(t) == bits(c)).all()
 
 
+def test_svd3_and_recover_pose_edge_matrices_vs_oracle(ctx, orc):
+    """essential matrices, diag(1, 1, 0) permuted, rank 1, negative determinant, permutations,
+    1e-30 and 1e30 scales, one NaN (tests/test_oracle_pinning.py builds them, pins the oracle to
+    the reference on them and states what holds there): the oracle's bits, a NaN being any NaN"""
+    from test_lba import same_bits
+    from test_oracle_pinning import svd_edge_matrices
+
+    for name, group in svd_edge_matrices().items():
+        for i, A in enumerate(group):
+            got = ctx.svd3_host(A) + ctx.recover_pose_host(A)
+            exp = orc.svd3(A) + orc.recover_pose(A)
+            assert all(same_bits(x, y) for x, y in zip(got, exp)), (name, i)
+
+
 def test_as_built_pose_constant(ctx):
     exp = load_golden("expected_outputs.npz")
     R1, R2, t = ctx.recover_pose_host(np.eye(3, dtype=np.float32))

@@ -4,8 +4,10 @@ CPU: the oracle's chain is pinned bit for bit by the reference's committed outpu
 (outputs/785/trajectory_000785_000789.ply as built, the older outputs/785/trajectory.ply by
 the 4x4 composition), the .pose.txt files to their printed 6 decimals, and the library's C
 writers reproduce the committed files byte for byte (host code: no device needed).
-GPU (marked): the chain kernel equals the oracle bit for bit, the rebase path (multi-GPU
-sharding) within float64 rounding, and mv_compute_trajectory writes the reference's files.
+GPU (marked): the chain kernel equals the oracle bit for bit (also at len 0, 1 and around its
+256-step LDS round, every start / mask / mode combination, guarded outputs), the rebase path
+(multi-GPU sharding) a numpy float64 restatement bit for bit and the unsplit chain within float64
+rounding, and mv_compute_trajectory writes the reference's files.
 A world-size-2 gloo test of the sharded chain lives in tests/test_dist.py."""
 import os
 
@@ -194,3 +196,125 @@ def test_gpu_compute_trajectory_writes_reference_files(ctx, tmp_path):
     out2.mkdir()
     assert ctx.compute_trajectory(785, 789, str(tmp_path), str(out2)) == 4
     assert not (out2 / "frame-000787.pose.txt").exists()
+
+
+# ------------------------------------------------------------------ edge lengths
+CHAIN_ROUND = 256  # k_trajectory.hip CHUNK: steps staged per LDS round
+CHAIN_LENS = [0, 1, 255, 256, 257, 512]
+REBASE_SHAPES = [(1, 255), (3, 85), (2, 128), (1, 257)]  # (batch, len1): k_rebase's 256-thread blocks
+
+
+def chain_case(n):
+    """batch of 3 sequences of n steps, a start per sequence, and masks: first step absent, last
+    step absent (both with a tenth of the others), all steps absent"""
+    rng = np.random.default_rng(1000 + n)
+    rel = np.stack([_rand_rel(rng, n) for _ in range(3)]).reshape(3, n, 3, 4)
+    start = np.stack([_rand_rel(rng, 1)[0] for _ in range(3)])
+    pres = (rng.random((3, n)) > 0.1).astype(np.int32)
+    if n:
+        pres[0, 0], pres[1, 0] = 0, 1
+        pres[0, -1], pres[1, -1] = (1, 0) if n > 1 else (0, 0)
+    pres[2] = 0
+    return rel, start, pres
+
+
+def rebase_case(batch, len1):
+    rng = np.random.default_rng(2000 + batch * len1)
+    poses = np.stack([_rand_rel(rng, len1) for _ in range(batch)]) * rng.uniform(0.5, 40, (batch, len1, 1, 1))
+    base = np.stack([_rand_rel(rng, 1)[0] for _ in range(batch)])
+    return base, poses
+
+
+def rebase_restated(base, poses, mode):
+    """k_rebase in numpy float64 (IEEE, no FMA), the kernel's stated order: two products added,
+    the third added, then the translation term.  base [B, 3, 4], poses [B, len1, 3, 4]."""
+    out = np.empty_like(poses)
+    for b in range(poses.shape[0]):
+        S, P = base[b], poses[b]
+        for r in range(3):
+            for c in range(4):
+                v = P[:, r, 0] * S[0, c]
+                v = v + P[:, r, 1] * S[1, c]
+                v = v + P[:, r, 2] * S[2, c]
+                if c == 3:
+                    v = v + P[:, r, 3] if mode == 1 else P[:, r, 3] + S[r, 3]
+                out[b, :, r, c] = v
+    return out
+
+
+def test_chain_and_rebase_cases_are_what_they_claim():
+    assert CHAIN_LENS == [0, 1, CHAIN_ROUND - 1, CHAIN_ROUND, CHAIN_ROUND + 1, 2 * CHAIN_ROUND]
+    for n in CHAIN_LENS:
+        rel, start, pres = chain_case(n)
+        assert rel.shape == (3, n, 3, 4) and pres.shape == (3, n) and not pres[2].any()
+        if n > 1:
+            assert pres[0, 0] == 0 and pres[0, -1] == 1 and pres[1, 0] == 1 and pres[1, -1] == 0
+            assert pres[:2].sum() >= n  # and most steps present
+    assert sorted({b * n for b, n in REBASE_SHAPES}) == [255, 256, 257]
+    assert any(b == 2 for b, n in REBASE_SHAPES)
+    for b, n in REBASE_SHAPES:
+        base, _ = rebase_case(b, n)
+        assert all((base[i] != base[j]).any() for i in range(b) for j in range(i))
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+def test_rebase_restatement_against_the_matrix_product(mode):
+    """independent of the kernel: MV_CHAIN_COMPOSE is the 4 x 4 float64 product pose . base to
+    1e-12 relative; MV_CHAIN_AS_BUILT has the product's rotation and adds the translations only"""
+    base, poses = rebase_case(2, 128)
+    got = rebase_restated(base, poses, mode)
+    for b in range(2):
+        S4 = np.vstack([base[b], [0, 0, 0, 1]])
+        for k in range(poses.shape[1]):
+            M = np.vstack([poses[b, k], [0, 0, 0, 1]]) @ S4
+            if mode == 0:
+                M[:3, 3] = poses[b, k, :, 3] + base[b, :, 3]
+                assert (got[b, k, :, 3] == M[:3, 3]).all()
+            assert np.abs(got[b, k] - M[:3]).max() <= 1e-12 * np.abs(M[:3]).max()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", CHAIN_LENS)
+def test_gpu_chain_edge_lengths(ctx, orc, torch_cuda, n):
+    """start given or NULL x present given or NULL x both modes, batch 3, guarded output"""
+    from test_gpu_tracks import Guarded
+
+    torch = torch_cuda
+    dev = torch.device("cuda:0")
+    rel, start, pres = chain_case(n)
+    d_rel, d_start, d_pres = (torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (rel, start, pres))
+    ctx.set_stream(torch.cuda.current_stream())
+    try:
+        for mode in (0, 1):
+            for with_start in (False, True):
+                for with_pres in (False, True):
+                    out = Guarded(torch, (3, n + 1, 3, 4), torch.float64)
+                    ctx.trajectory_chain(d_rel, out.t, d_pres if with_pres else None, d_start if with_start else None,
+                                         mode)
+                    torch.cuda.synchronize()
+                    got = out.np()
+                    for b in range(3):
+                        exp = orc.trajectory_chain(rel[b], present=pres[b] if with_pres else None,
+                                                   start=start[b] if with_start else None, mode=mode)
+                        assert (got[b].view(np.int64) == exp.view(np.int64)).all(), (mode, with_start, with_pres, b)
+    finally:
+        ctx.set_stream(None)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("batch,len1", REBASE_SHAPES)
+def test_gpu_rebase_bit_exact(ctx, torch_cuda, batch, len1):
+    from test_gpu_tracks import Guarded
+
+    torch = torch_cuda
+    base, poses = rebase_case(batch, len1)
+    ctx.set_stream(torch.cuda.current_stream())
+    try:
+        for mode in (0, 1):
+            buf = Guarded(torch, (batch, len1, 3, 4), torch.float64)
+            buf.t.copy_(torch.from_numpy(poses))
+            ctx.trajectory_rebase(torch.from_numpy(base).to("cuda:0"), buf.t, mode)
+            torch.cuda.synchronize()
+            assert (buf.np().view(np.int64) == rebase_restated(base, poses, mode).view(np.int64)).all(), mode
+    finally:
+        ctx.set_stream(None)
