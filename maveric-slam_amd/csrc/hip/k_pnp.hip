@@ -3,23 +3,25 @@
 //
 // k_pnp_gather: one workgroup per problem, one wave-ballot compaction (tr::block_rank) per 256 rows.
 // k_pnp_solve:  one 256-thread workgroup per problem, a grid-stride loop over the problems.
-//   stage      the valid pairs, promoted once to float64, into LDS (structure of arrays) by the same
-//              ballot compaction, with each pair's index in the input.
-//   hypotheses thread t owns hypothesis t (thread 0 the prior as well): its draws and its P3P sit
-//              in registers -- every small vector is named scalars or a fully unrolled array, so
-//              nothing is indexed at run time and nothing goes to scratch memory (the lesson of
-//              k_pose_intended.hip); the fp32 pose goes to LDS.
-//   subset     every thread scores its pose on the 64-pair subset; a pair is read by the whole
-//              wave from one LDS address (a broadcast).
-//   select     each owner ranks its (cost, h) key against the 257 keys in LDS; ranks 0..7 survive.
-//   full score a survivor at a time: thread t adds the pairs t, t + 256, ..., thread 0 adds the 256
-//              partials in ascending order (the solvers' fixed tree, mv_lm.hpp).
-//   refine     per round: inlier flags in LDS, then the LM: thread t linearises its pairs
-//              (pf_linearize.hpp) and keeps 27 partial sums in registers, which go to a [27][256]
-//              slab of the context scratch; threads 0..26 add one entry each in ascending order
-//              between the tree's barriers; thread 0 damps, factors the 6 x 6 system in LDS
-//              (right-hand side as row 6), retracts and decides; the candidate's cost by the tree.
-//              Loss, tree, retraction and decision are mv_lm.hpp's, as in k_ba_solve and k_pg_solve.
+//   stage_pairs      the valid pairs, promoted once to float64, into LDS (structure of arrays) by the
+//                    same ballot compaction, with each pair's index in the input.
+//   hypotheses       thread t owns hypothesis t (thread 0 the prior as well): its draws and its P3P
+//                    sit in registers -- every small vector is named scalars or a fully unrolled
+//                    array, so nothing is indexed at run time and nothing goes to scratch memory (the
+//                    lesson of k_pose_intended.hip); the fp32 pose goes to LDS.  Then every thread
+//                    scores its pose on the 64-pair subset; a pair is read by the whole wave from one
+//                    LDS address (a broadcast).
+//   rank_survivors   each owner ranks its (cost, h) key against the 257 keys in LDS; ranks 0..7 survive.
+//   score_survivors  a survivor at a time by score_all: thread t adds the pairs t, t + 256, ..., thread
+//                    0 adds the 256 partials in ascending order (the solvers' fixed tree, mv_lm.hpp).
+//   refine           per round: inlier flags in LDS (score_all), then mv::lm_run on PnpProblem:
+//                    linearize -- thread t linearises its pairs (pf_linearize.hpp) and keeps 27
+//                    partial sums in registers, which go to a [27][256] slab of the context scratch;
+//                    threads 0..26 add one entry each in ascending order between the tree's barriers;
+//                    the candidate's cost by the tree --, step -- thread 0 damps, factors the 6 x 6
+//                    system in LDS (right-hand side as row 6) and retracts -- and accept.  Protocol,
+//                    loss, tree, retraction and decision are mv_lm.hpp's, as in k_ba_solve.
+//   output           the pose, the inlier flags and the figures; of a failed problem the prior.
 // All arithmetic is float64 in the order of tests/pnp_reference.py (-ffp-contract=off).
 // LDS: 45 B per pair of `cap` (dynamic) + 11.5 KiB (sum tree, keys, hypothesis poses, 6 x 6).
 #include <math.h>
@@ -214,24 +216,36 @@ __device__ bool p3p_best(V3 X1, V3 X2, V3 X3, V3 r1, V3 r2, V3 r3, V3 X4, double
     return have;
 }
 
+struct PnpShared {
+    alignas(16) double part[NT];  // the cost tree; 16 B as a __shared__ array of its own has: 128-bit reads
+    double key[NE], full[MV_PNP_SURVIVORS], H[NH], L[28], x[6];
+    float hp[NE][7], pose[7], cand[7], prior[7];
+    int surv[MV_PNP_SURVIVORS], wc[NT / 64], m, win, cnt;
+    mv::LmShared lm;
+    double out;
+};
+
 // the workgroup's view of one problem
 struct Prob {
-    int m;  // valid pairs
-    const double *X0, *X1, *X2, *U, *V;  // LDS, [m]
+    int m;                          // valid pairs
+    double *X0, *X1, *X2, *U, *V;   // dynamic LDS [cap], the valid pairs in [m]
+    int *vidx;                      // dynamic LDS [cap]: a valid pair's index in the input
+    unsigned char *inl;             // dynamic LDS [cap]: inlier flags
+    double *Hp;                     // this workgroup's slice of PnpScratch
+    PnpShared *S;
     Cam K;
     float Kf[4];
     double thr2, min_depth;
 };
 
-// msac over all valid pairs at `pose` (LDS or global, [7]) by the tree; with flags, the inlier flags
-// to inl and their number to *cnt.  *out and *cnt are LDS; ends with a barrier.
-__device__ void score_all(const Prob &Q, const float *pose, bool flags, unsigned char *inl, double *s_part,
-                          double *out, int *cnt) {
+// msac over all valid pairs at `pose` (LDS or global, [7]) by the tree to *out (LDS); with flags, the
+// inlier flags to Q.inl and their number to S.cnt.  Ends with a barrier.
+__device__ void score_all(const Prob &Q, const float *pose, bool flags, double *out) {
     const int tid = threadIdx.x;
     PoseRt P;
     pose_rt(pose, P);
     __syncthreads();  // every thread is done with the last count
-    if (tid == 0) *cnt = 0;
+    if (tid == 0) Q.S->cnt = 0;
     __syncthreads();
     double part = 0.0;
     int c = 0;
@@ -240,18 +254,18 @@ __device__ void score_all(const Prob &Q, const float *pose, bool flags, unsigned
         pair_err(P, Q.K, Q.X0[k], Q.X1[k], Q.X2[k], Q.U[k], Q.V[k], e2, depth);
         const bool in = depth >= Q.min_depth && e2 <= Q.thr2;
         part = part + (in ? e2 : Q.thr2);
-        if (flags) inl[k] = in ? 1 : 0;
+        if (flags) Q.inl[k] = in ? 1 : 0;
         c += in ? 1 : 0;
     }
-    if (flags && c) atomicAdd(cnt, c);
-    mv::tree_sum_256(part, s_part, out);
+    if (flags && c) atomicAdd(&Q.S->cnt, c);
+    mv::tree_sum_256(part, Q.S->part, out);
 }
 
 // Linearise the inliers at `pose` [7]: the cost to *out by the tree; with jac the 27 sums of the
-// normal equations to s_H (the lower triangle row by row, then -J^T W e).  Ends with a barrier.
-__device__ void linearize(const Prob &Q, const float *pose, const unsigned char *inl, bool jac, double huber,
-                          double *s_part, double *Hp, double *s_H, double *out) {
+// normal equations to S.H (the lower triangle row by row, then -J^T W e).  Ends with a barrier.
+__device__ void linearize(const Prob &Q, const float *pose, bool jac, double huber, double *out) {
     const int tid = threadIdx.x;
+    double *const Hp = Q.Hp;
     float T[7];
 #pragma unroll
     for (int i = 0; i < 7; i++) T[i] = pose[i];
@@ -260,7 +274,7 @@ __device__ void linearize(const Prob &Q, const float *pose, const unsigned char 
 #pragma unroll
     for (int i = 0; i < NH; i++) hp[i] = 0.0;
     for (int k = tid; k < Q.m; k += NT) {
-        if (!inl[k]) continue;
+        if (!Q.inl[k]) continue;
         const float X[3] = {(float)Q.X0[k], (float)Q.X1[k], (float)Q.X2[k]};  // exact: promoted fp32
         float J[20];
         mv::pf_linearize(X, T, Q.Kf, (float)Q.U[k], (float)Q.V[k], jac, J);
@@ -286,13 +300,220 @@ __device__ void linearize(const Prob &Q, const float *pose, const unsigned char 
 #pragma unroll
         for (int i = 0; i < NH; i++) Hp[i * NT + tid] = hp[i];
     }
-    mv::tree_sum_256(part, s_part, out, [&] {  // between the tree's barriers: the 27 sums
+    mv::tree_sum_256(part, Q.S->part, out, [&] {  // between the tree's barriers: the 27 sums
         if (jac && tid < NH) {
             double c = 0.0;
             for (int i = 0; i < NT; i++) c = c + Hp[tid * NT + i];
-            s_H[tid] = tid < 21 ? c : 0.0 - c;
+            Q.S->H[tid] = tid < 21 ? c : 0.0 - c;
         }
     });
+}
+
+// The prior (or the identity) to LDS, the inlier output cleared, and the valid pairs of the first n
+// staged in ascending order; sets Q.m.
+__device__ __forceinline__ void stage_pairs(Prob &Q, int n, const float *p3, const float *p2, const float *prior,
+                                            int *inl_out, int cap) {
+    const int tid = threadIdx.x;
+    PnpShared &S = *Q.S;
+    if (tid < 7) S.prior[tid] = prior ? prior[tid] : (tid == 0 ? 1.f : 0.f);
+    if (tid == 0) S.m = 0;
+    for (int i = tid; i < cap; i += NT) inl_out[i] = 0;
+    __syncthreads();
+    for (int base = 0; base < n; base += NT) {
+        const int i = base + tid;
+        float a0 = 0.f, a1 = 0.f, a2 = 0.f, b0 = 0.f, b1 = 0.f;
+        bool valid = false;
+        if (i < n) {
+            a0 = p3[3l * i], a1 = p3[3l * i + 1], a2 = p3[3l * i + 2], b0 = p2[2l * i], b1 = p2[2l * i + 1];
+            valid = isfinite(a0) && isfinite(a1) && isfinite(a2) && isfinite(b0) && isfinite(b1);
+        }
+        const int off = S.m + tr::block_rank(valid, S.wc);
+        if (valid) {
+            Q.X0[off] = a0, Q.X1[off] = a1, Q.X2[off] = a2, Q.U[off] = b0, Q.V[off] = b1;
+            Q.vidx[off] = i;
+        }
+        __syncthreads();
+        if (tid == 0) S.m = S.m + S.wc[0] + S.wc[1] + S.wc[2] + S.wc[3];
+        __syncthreads();
+    }
+    Q.m = S.m;
+}
+
+// Hypotheses and their subset costs to S.hp / S.key: entry tid + 1, and the prior (entry 0) by
+// thread 0.  Ends with a barrier.
+__device__ __forceinline__ void hypotheses(const Prob &Q, const mv_pnp_params &P, bool have_prior) {
+    const int tid = threadIdx.x, m = Q.m;
+    PnpShared &S = *Q.S;
+    const double *const X0 = Q.X0, *const X1 = Q.X1, *const X2 = Q.X2, *const U = Q.U, *const V = Q.V;
+    const int msub = min(m, MV_PNP_SUBSET);
+    for (int pass = 0; pass < 2; pass++) {
+        if (pass == 1 && tid != 0) break;
+        const int e = pass == 0 ? tid + 1 : 0;
+        float pose[7] = {1.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        bool ok = false;
+        if (e == 0) {
+            ok = have_prior;
+#pragma unroll
+            for (int i = 0; i < 7; i++) {
+                pose[i] = S.prior[i];
+                ok = ok && isfinite(pose[i]);
+            }
+        } else if (tid < P.hypotheses) {
+            const unsigned long long base = P.seed ^ ((unsigned long long)tid << 8);
+            int i0 = 0, i1 = 0, i2 = 0, i3 = 0, drawn = 0;
+            unsigned long long r = 0;
+            for (int d = 0; d < 64 && drawn < 4; d++) {  // two 32-bit draws per splitmix64 output
+                if ((d & 1) == 0) r = splitmix64(base + (unsigned long long)(d >> 1));
+                const unsigned u = (d & 1) ? (unsigned)r : (unsigned)(r >> 32);
+                const int c = (int)(((unsigned long long)u * (unsigned)m) >> 32);
+                const bool dup = (drawn > 0 && c == i0) || (drawn > 1 && c == i1) || (drawn > 2 && c == i2);
+                if (!dup) {
+                    if (drawn == 0) i0 = c;
+                    if (drawn == 1) i1 = c;
+                    if (drawn == 2) i2 = c;
+                    if (drawn == 3) i3 = c;
+                    drawn++;
+                }
+            }
+            if (drawn == 4) {
+                const V3 A = {X0[i0], X1[i0], X2[i0]}, B = {X0[i1], X1[i1], X2[i1]}, C = {X0[i2], X1[i2], X2[i2]};
+                const V3 D = {X0[i3], X1[i3], X2[i3]};
+                ok = p3p_best(A, B, C, bearing(U[i0], V[i0], Q.K), bearing(U[i1], V[i1], Q.K),
+                              bearing(U[i2], V[i2], Q.K), D, U[i3], V[i3], Q.K, pose);
+            }
+        }
+        double c = __builtin_inf();
+        if (ok) {
+            PoseRt R;
+            pose_rt(pose, R);
+            c = 0.0;
+            for (int k = 0; k < msub; k++) {
+                const int i = (int)(((long)k * m) / MV_PNP_SUBSET);
+                double e2, depth;
+                pair_err(R, Q.K, X0[i], X1[i], X2[i], U[i], V[i], e2, depth);
+                c = c + ((depth >= Q.min_depth && e2 <= Q.thr2) ? e2 : Q.thr2);
+            }
+        }
+        S.key[e] = c;
+#pragma unroll
+        for (int i = 0; i < 7; i++) S.hp[e][i] = pose[i];
+    }
+    if (tid < MV_PNP_SURVIVORS) S.surv[tid] = -1;
+    __syncthreads();
+}
+
+// The 8 lowest (cost, entry) to S.surv: each owner ranks its key.  Ends with a barrier.
+__device__ __forceinline__ void rank_survivors(const Prob &Q) {
+    const int tid = threadIdx.x;
+    PnpShared &S = *Q.S;
+    for (int pass = 0; pass < 2; pass++) {
+        if (pass == 1 && tid != 0) break;
+        const int e = pass == 0 ? tid + 1 : 0;
+        const double c = S.key[e];
+        if (!(c < __builtin_inf())) continue;
+        int rank = 0;
+        for (int j = 0; j < NE; j++) {
+            const double cj = S.key[j];
+            rank += (cj < c || (cj == c && j < e)) ? 1 : 0;
+        }
+        if (rank < MV_PNP_SURVIVORS) S.surv[rank] = e;
+    }
+    __syncthreads();
+}
+
+// Every survivor scored on all pairs; the lowest (cost, entry) to S.win, -1 when there is none, and
+// returned after a barrier.
+__device__ __forceinline__ int score_survivors(const Prob &Q) {
+    PnpShared &S = *Q.S;
+    for (int k = 0; k < MV_PNP_SURVIVORS; k++) {
+        const int e = S.surv[k];
+        if (e < 0) break;  // uniform
+        score_all(Q, S.hp[e], false, &S.full[k]);
+    }
+    if (threadIdx.x == 0) {
+        int win = -1;
+        double best = __builtin_inf();
+        for (int k = 0; k < MV_PNP_SURVIVORS; k++) {
+            const int e = S.surv[k];
+            if (e < 0) break;
+            if (win < 0 || S.full[k] < best || (S.full[k] == best && e < win)) win = e, best = S.full[k];
+        }
+        S.win = win;
+    }
+    __syncthreads();
+    return S.win;
+}
+
+// What mv::lm_run asks of a solver: the pose-only LM over the inliers in Q.inl, S.pose -> S.pose.
+struct PnpProblem {
+    const Prob &Q;
+    double huber;
+    __device__ __forceinline__ void linearize(bool at_candidate, bool jac, double *out) const {
+        ::linearize(Q, at_candidate ? Q.S->cand : Q.S->pose, jac, huber, out);
+    }
+    // thread 0: damp; Cholesky with the right-hand side as row 6; back-substitute; retract
+    __device__ __forceinline__ void step(double lam, double floor_) const {
+        PnpShared &S = *Q.S;
+        if (threadIdx.x == 0) {
+            for (int i = 0; i < 28; i++) S.L[i] = S.H[i];
+            for (int i = 0; i < 6; i++) {
+                const double d = S.L[tri(i, i)];
+                S.L[tri(i, i)] = d + lam * dmax(d, floor_);
+            }
+            for (int j = 0; j < 6; j++) {
+                for (int i = j; i < 7; i++) {
+                    double acc = S.L[tri(i, j)];
+                    for (int k = 0; k < j; k++) acc = acc - S.L[tri(i, k)] * S.L[tri(j, k)];
+                    if (i == j) {
+                        if (!(acc > 0.0) || !isfinite(acc)) S.lm.fail = 1;
+                        S.L[tri(j, j)] = sqrt(acc);
+                    } else {
+                        S.L[tri(i, j)] = acc / S.L[tri(j, j)];
+                    }
+                }
+            }
+            for (int i = 5; i >= 0; i--) {
+                double acc = S.L[tri(6, i)];
+                for (int k = i + 1; k < 6; k++) acc = acc - S.L[tri(k, i)] * S.x[k];
+                S.x[i] = acc / S.L[tri(i, i)];
+            }
+            mv::retract_pose(S.x, S.pose, S.cand);
+        }
+        __syncthreads();
+    }
+    __device__ __forceinline__ void accept() const {
+        if (threadIdx.x < 7) Q.S->pose[threadIdx.x] = Q.S->cand[threadIdx.x];
+    }
+};
+
+// The refinement rounds on S.pose: the inlier flags at the pose, then the LM over them.
+__device__ __forceinline__ void refine(const Prob &Q, const mv_pnp_params &P) {
+    PnpShared &S = *Q.S;
+    for (int round = 0; round < P.refine_rounds; round++) {
+        score_all(Q, S.pose, true, &S.out);
+        if (S.cnt == 0) continue;  // uniform
+        mv::lm_run(P, S.lm, PnpProblem{Q, P.huber_px});
+        __syncthreads();
+    }
+}
+
+// The pose, the inlier flags and the figures of a solved problem; of a failed one the prior and its status.
+__device__ __forceinline__ void output(const Prob &Q, int s, int st, int cap, float *pose_out, int *inlier,
+                                       int *num_inliers, int *best_hyp, int *status, double *cost) {
+    const int tid = threadIdx.x;
+    const PnpShared &S = *Q.S;
+    if (st == MV_OK) {
+        for (int k = tid; k < Q.m; k += NT) inlier[(size_t)s * cap + Q.vidx[k]] = Q.inl[k];
+        if (tid < 7) pose_out[(size_t)s * 7 + tid] = S.pose[tid];
+    } else if (tid < 7) {
+        pose_out[(size_t)s * 7 + tid] = S.prior[tid];
+    }
+    if (tid == 0) {
+        status[s] = st;
+        num_inliers[s] = st == MV_OK ? S.cnt : 0;
+        best_hyp[s] = st == MV_OK ? S.win - 1 : -2;
+        cost[s] = st == MV_OK ? S.out : 0.0;
+    }
 }
 
 __global__ __launch_bounds__(NT) void k_pnp_solve(mv_pnp_params P, int batch, int cap, const int *__restrict__ nArr,
@@ -302,219 +523,42 @@ __global__ __launch_bounds__(NT) void k_pnp_solve(mv_pnp_params P, int batch, in
                                                   int *__restrict__ best_hyp, int *__restrict__ status,
                                                   double *__restrict__ cost, PnpScratch scr) {
     extern __shared__ double s_dyn[];  // X0 X1 X2 U V [cap] doubles, vidx [cap] ints, inl [cap] bytes
-    __shared__ double s_part[NT], s_key[NE], s_full[MV_PNP_SURVIVORS], s_H[NH], s_L[28], s_x[6];
-    __shared__ float s_hp[NE][7], s_pose[7], s_cand[7], s_prior[7];
-    __shared__ int s_surv[MV_PNP_SURVIVORS], s_wc[NT / 64], s_m, s_win, s_cnt;
-    __shared__ int s_fail;
-    __shared__ mv::LmState s_lm;
-    __shared__ double s_candc, s_out;
+    __shared__ PnpShared S;
     const int tid = threadIdx.x;
-    double *const X0 = s_dyn, *const X1 = X0 + cap, *const X2 = X1 + cap, *const U = X2 + cap, *const V = U + cap;
-    int *const vidx = reinterpret_cast<int *>(V + cap);
-    unsigned char *const inl = reinterpret_cast<unsigned char *>(vidx + cap);
-    double *const Hp = scr.Hp + (size_t)blockIdx.x * NH * NT;
-    const double inf = __builtin_inf();
+    Prob Q;
+    Q.X0 = s_dyn, Q.X1 = Q.X0 + cap, Q.X2 = Q.X1 + cap, Q.U = Q.X2 + cap, Q.V = Q.U + cap;
+    Q.vidx = reinterpret_cast<int *>(Q.V + cap);
+    Q.inl = reinterpret_cast<unsigned char *>(Q.vidx + cap);
+    Q.Hp = scr.Hp + (size_t)blockIdx.x * NH * NT, Q.S = &S;
+    Q.thr2 = P.inlier_thresh_px * P.inlier_thresh_px, Q.min_depth = P.min_depth;
 
     for (int s = blockIdx.x; s < batch; s += gridDim.x) {
         __syncthreads();  // the previous problem's shared state is done with
-        const int n = min(max(nArr[s], 0), cap);
-        const float *p3 = pts3 + (size_t)s * cap * 3, *p2 = pts2 + (size_t)s * cap * 2;
-        int *const inl_out = inlier + (size_t)s * cap;
-        if (tid < 7) s_prior[tid] = prior ? prior[(size_t)s * 7 + tid] : (tid == 0 ? 1.f : 0.f);
-        if (tid == 0) s_m = 0;
-        for (int i = tid; i < cap; i += NT) inl_out[i] = 0;
-        __syncthreads();
-        // stage the valid pairs in ascending order
-        for (int base = 0; base < n; base += NT) {
-            const int i = base + tid;
-            float a0 = 0.f, a1 = 0.f, a2 = 0.f, b0 = 0.f, b1 = 0.f;
-            bool valid = false;
-            if (i < n) {
-                a0 = p3[3l * i], a1 = p3[3l * i + 1], a2 = p3[3l * i + 2], b0 = p2[2l * i], b1 = p2[2l * i + 1];
-                valid = isfinite(a0) && isfinite(a1) && isfinite(a2) && isfinite(b0) && isfinite(b1);
-            }
-            const int off = s_m + tr::block_rank(valid, s_wc);
-            if (valid) {
-                X0[off] = a0, X1[off] = a1, X2[off] = a2, U[off] = b0, V[off] = b1;
-                vidx[off] = i;
-            }
-            __syncthreads();
-            if (tid == 0) s_m = s_m + s_wc[0] + s_wc[1] + s_wc[2] + s_wc[3];
-            __syncthreads();
-        }
-        const int m = s_m;
-        int st = MV_OK;
-        if (m < 4) st = MV_ERR_NO_POINTS;
-
-        Prob Q;
-        Q.m = m, Q.X0 = X0, Q.X1 = X1, Q.X2 = X2, Q.U = U, Q.V = V;
+        stage_pairs(Q, min(max(nArr[s], 0), cap), pts3 + (size_t)s * cap * 3, pts2 + (size_t)s * cap * 2,
+                    prior ? prior + (size_t)s * 7 : nullptr, inlier + (size_t)s * cap, cap);
 #pragma unroll
         for (int i = 0; i < 4; i++) Q.Kf[i] = cams[(size_t)s * 4 + i];
         Q.K = {(double)Q.Kf[0], (double)Q.Kf[1], (double)Q.Kf[2], (double)Q.Kf[3]};
-        Q.thr2 = P.inlier_thresh_px * P.inlier_thresh_px, Q.min_depth = P.min_depth;
 
+        // st is the same in every thread throughout
+        int st = Q.m < 4 ? MV_ERR_NO_POINTS : MV_OK;
         if (st == MV_OK) {
-            // hypotheses and their subset costs: entry tid + 1, and the prior (entry 0) by thread 0
-            const int msub = min(m, MV_PNP_SUBSET);
-            for (int pass = 0; pass < 2; pass++) {
-                if (pass == 1 && tid != 0) break;
-                const int e = pass == 0 ? tid + 1 : 0;
-                float pose[7] = {1.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-                bool ok = false;
-                if (e == 0) {
-                    ok = prior != nullptr;
-#pragma unroll
-                    for (int i = 0; i < 7; i++) {
-                        pose[i] = s_prior[i];
-                        ok = ok && isfinite(pose[i]);
-                    }
-                } else if (tid < P.hypotheses) {
-                    const unsigned long long base = P.seed ^ ((unsigned long long)tid << 8);
-                    int i0 = 0, i1 = 0, i2 = 0, i3 = 0, drawn = 0;
-                    unsigned long long r = 0;
-                    for (int d = 0; d < 64 && drawn < 4; d++) {  // two 32-bit draws per splitmix64 output
-                        if ((d & 1) == 0) r = splitmix64(base + (unsigned long long)(d >> 1));
-                        const unsigned u = (d & 1) ? (unsigned)r : (unsigned)(r >> 32);
-                        const int c = (int)(((unsigned long long)u * (unsigned)m) >> 32);
-                        const bool dup = (drawn > 0 && c == i0) || (drawn > 1 && c == i1) || (drawn > 2 && c == i2);
-                        if (!dup) {
-                            if (drawn == 0) i0 = c;
-                            if (drawn == 1) i1 = c;
-                            if (drawn == 2) i2 = c;
-                            if (drawn == 3) i3 = c;
-                            drawn++;
-                        }
-                    }
-                    if (drawn == 4) {
-                        const V3 A = {X0[i0], X1[i0], X2[i0]}, B = {X0[i1], X1[i1], X2[i1]}, C = {X0[i2], X1[i2], X2[i2]};
-                        const V3 D = {X0[i3], X1[i3], X2[i3]};
-                        ok = p3p_best(A, B, C, bearing(U[i0], V[i0], Q.K), bearing(U[i1], V[i1], Q.K),
-                                      bearing(U[i2], V[i2], Q.K), D, U[i3], V[i3], Q.K, pose);
-                    }
-                }
-                double c = inf;
-                if (ok) {
-                    PoseRt R;
-                    pose_rt(pose, R);
-                    c = 0.0;
-                    for (int k = 0; k < msub; k++) {
-                        const int i = (int)(((long)k * m) / MV_PNP_SUBSET);
-                        double e2, depth;
-                        pair_err(R, Q.K, X0[i], X1[i], X2[i], U[i], V[i], e2, depth);
-                        c = c + ((depth >= Q.min_depth && e2 <= Q.thr2) ? e2 : Q.thr2);
-                    }
-                }
-                s_key[e] = c;
-#pragma unroll
-                for (int i = 0; i < 7; i++) s_hp[e][i] = pose[i];
-            }
-            if (tid < MV_PNP_SURVIVORS) s_surv[tid] = -1;
-            __syncthreads();
-            // the 8 lowest (cost, entry): each owner ranks its key
-            for (int pass = 0; pass < 2; pass++) {
-                if (pass == 1 && tid != 0) break;
-                const int e = pass == 0 ? tid + 1 : 0;
-                const double c = s_key[e];
-                if (!(c < inf)) continue;
-                int rank = 0;
-                for (int j = 0; j < NE; j++) {
-                    const double cj = s_key[j];
-                    rank += (cj < c || (cj == c && j < e)) ? 1 : 0;
-                }
-                if (rank < MV_PNP_SURVIVORS) s_surv[rank] = e;
-            }
-            __syncthreads();
-            for (int k = 0; k < MV_PNP_SURVIVORS; k++) {
-                const int e = s_surv[k];
-                if (e < 0) break;  // uniform
-                score_all(Q, s_hp[e], false, inl, s_part, &s_full[k], &s_cnt);
-            }
-            if (tid == 0) {
-                int win = -1;
-                double best = inf;
-                for (int k = 0; k < MV_PNP_SURVIVORS; k++) {
-                    const int e = s_surv[k];
-                    if (e < 0) break;
-                    if (win < 0 || s_full[k] < best || (s_full[k] == best && e < win)) win = e, best = s_full[k];
-                }
-                s_win = win;
-            }
-            __syncthreads();
-            if (s_win < 0) st = MV_ERR_DEGENERATE;
+            hypotheses(Q, P, prior != nullptr);
+            rank_survivors(Q);
+            if (score_survivors(Q) < 0) st = MV_ERR_DEGENERATE;
         }
         if (st == MV_OK) {
-            if (tid < 7) s_pose[tid] = s_hp[s_win][tid];
+            if (tid < 7) S.pose[tid] = S.hp[S.win][tid];
             __syncthreads();
-            score_all(Q, s_pose, true, inl, s_part, &s_out, &s_cnt);
-            if (s_cnt < P.min_inliers) st = MV_ERR_DEGENERATE;
+            score_all(Q, S.pose, true, &S.out);
+            if (S.cnt < P.min_inliers) st = MV_ERR_DEGENERATE;
         }
         if (st == MV_OK) {
-            for (int round = 0; round < P.refine_rounds; round++) {
-                score_all(Q, s_pose, true, inl, s_part, &s_out, &s_cnt);
-                if (s_cnt == 0) continue;  // uniform
-                if (tid == 0) {
-                    mv::lm_reset(s_lm, P.lambda_init);
-                    s_fail = 0;
-                }
-                linearize(Q, s_pose, inl, true, P.huber_px, s_part, Hp, s_H, &s_lm.cost);
-                for (int it = 0; it < P.max_iters; it++) {
-                    if (s_lm.stop) break;  // uniform: written before the last barrier
-                    if (s_lm.relin) linearize(Q, s_pose, inl, true, P.huber_px, s_part, Hp, s_H, &s_lm.cost);
-                    const double lam = s_lm.lambda;
-                    if (tid == 0) {
-                        // damp; Cholesky with the right-hand side as row 6; back-substitute; retract
-                        for (int i = 0; i < 28; i++) s_L[i] = s_H[i];
-                        for (int i = 0; i < 6; i++) {
-                            const double d = s_L[tri(i, i)];
-                            s_L[tri(i, i)] = d + lam * dmax(d, P.diag_floor);
-                        }
-                        for (int j = 0; j < 6; j++) {
-                            for (int i = j; i < 7; i++) {
-                                double acc = s_L[tri(i, j)];
-                                for (int k = 0; k < j; k++) acc = acc - s_L[tri(i, k)] * s_L[tri(j, k)];
-                                if (i == j) {
-                                    if (!(acc > 0.0) || !isfinite(acc)) s_fail = 1;
-                                    s_L[tri(j, j)] = sqrt(acc);
-                                } else {
-                                    s_L[tri(i, j)] = acc / s_L[tri(j, j)];
-                                }
-                            }
-                        }
-                        for (int i = 5; i >= 0; i--) {
-                            double acc = s_L[tri(6, i)];
-                            for (int k = i + 1; k < 6; k++) acc = acc - s_L[tri(k, i)] * s_x[k];
-                            s_x[i] = acc / s_L[tri(i, i)];
-                        }
-                        mv::retract_pose(s_x, s_pose, s_cand);
-                    }
-                    __syncthreads();
-                    linearize(Q, s_cand, inl, false, P.huber_px, s_part, Hp, s_H, &s_candc);
-                    if (tid == 0) {
-                        mv::lm_decide(P, s_lm, s_fail != 0, s_candc);
-                        s_fail = 0;
-                    }
-                    __syncthreads();
-                    if (s_lm.acc && tid < 7) s_pose[tid] = s_cand[tid];
-                    __syncthreads();
-                }
-                __syncthreads();
-            }
-            score_all(Q, s_pose, true, inl, s_part, &s_out, &s_cnt);
-            if (s_cnt < P.min_inliers) st = MV_ERR_DEGENERATE;
+            refine(Q, P);
+            score_all(Q, S.pose, true, &S.out);
+            if (S.cnt < P.min_inliers) st = MV_ERR_DEGENERATE;
         }
-        // uniform from here: st is the same in every thread
-        if (st == MV_OK) {
-            for (int k = tid; k < m; k += NT) inl_out[vidx[k]] = inl[k];
-            if (tid < 7) pose_out[(size_t)s * 7 + tid] = s_pose[tid];
-        } else if (tid < 7) {
-            pose_out[(size_t)s * 7 + tid] = s_prior[tid];
-        }
-        if (tid == 0) {
-            status[s] = st;
-            num_inliers[s] = st == MV_OK ? s_cnt : 0;
-            best_hyp[s] = st == MV_OK ? s_win - 1 : -2;
-            cost[s] = st == MV_OK ? s_out : 0.0;
-        }
+        output(Q, s, st, cap, pose_out, inlier, num_inliers, best_hyp, status, cost);
     }
 }
 

@@ -3,10 +3,14 @@
 // float64 in the restatements' order (-ffp-contract=off): every expression here keeps the
 // parenthesisation that tests/lba_reference.py, pgo_reference.py and pnp_reference.py state.
 //   device  R(q), the float64 quaternion product, the pose retraction, the Huber loss, the cost's
-//           fixed tree, and the accept / reject decision on an LmState in LDS.
+//           fixed tree, thread 0's accept / reject decision; the iteration protocol (lm_run over
+//           an LmShared in LDS) of k_ba_solve and k_pnp_solve -- k_pg_solve runs the same protocol in
+//           its own body (DESIGN 4.12 says why) --; the held rule, the candidate poses and the
+//           result write of a solver over many poses.
 //   host    the checks and defaults of the LM fields of mv_ba_params / mv_pg_params / mv_pnp_params,
 //           and the workgroup count of a grid-stride solver.
-// A solver supplies its own linearize (its factor kind), its linear solve and its state copy.
+// A solver supplies what lm_run's Problem lists: linearize (its factor kind), step (its linear
+// solve and its candidate) and accept (its state copy).
 // quat_rot is also the R(q) of the triangulation (tr_midpoint.hpp) and of k_map_match.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -127,6 +131,86 @@ __device__ __forceinline__ void lm_decide(const Params &P, LmState &L, bool fail
         if (L.lambda > P.lambda_max) L.stop = 1;
         L.relin = 0, L.acc = 0;
     }
+}
+
+// What one problem's iterations keep in LDS.  fail is set by any thread whose linear solve meets a
+// bad pivot; the rest is thread 0's, read by all after a barrier.
+struct LmShared {
+    LmState lm;
+    double cand;  // the candidate's cost
+    int fail, iters;
+};
+
+// The iterations of one problem, by the whole workgroup; returns the initial cost.  Problem:
+//   linearize(at_candidate, jac, out)  the cost of the state (or of the candidate) to *out by
+//                                      tree_sum_256, with jac the linearisation for step; ends with
+//                                      a barrier
+//   step(lambda, floor)                the damped system built and solved, S.fail set on a pivot that
+//                                      is not positive and finite, the candidate written; ends with
+//                                      a barrier
+//   accept()                           the candidate copied over the state, by all threads
+// Nothing else happens here, and the only barriers are the two around the copy.  Every exit is
+// uniform: stop is written before the last barrier.  After a rejected step the linearisation is
+// kept: at the same fp32 state it is the same bits.
+template <class Params, class Problem>
+__device__ __forceinline__ double lm_run(const Params &P, LmShared &S, const Problem &problem) {
+    if (threadIdx.x == 0) {
+        lm_reset(S.lm, P.lambda_init);
+        S.fail = 0, S.iters = 0;
+    }
+    problem.linearize(false, true, &S.lm.cost);
+    const double cost_initial = S.lm.cost;
+    for (int it = 0; it < P.max_iters; it++) {
+        if (S.lm.stop) break;
+        if (S.lm.relin) problem.linearize(false, true, &S.lm.cost);
+        problem.step(S.lm.lambda, P.diag_floor);
+        problem.linearize(true, false, &S.cand);
+        if (threadIdx.x == 0) {
+            S.iters = S.iters + 1;
+            lm_decide(P, S.lm, S.fail != 0, S.cand);
+            S.fail = 0;
+        }
+        __syncthreads();
+        if (S.lm.acc) problem.accept();
+        __syncthreads();
+    }
+    return cost_initial;
+}
+
+// Pose i of a problem (its index in `fixed`: g) is held when the caller fixed it -- without
+// `fixed`, the first one -- or when no factor sees it.
+__device__ __forceinline__ bool lm_held(const int *fixed, size_t g, int i, bool no_factor) {
+    return (fixed ? fixed[g] != 0 : i == 0) || no_factor;
+}
+
+// The candidate poses cand [n][7] of the step x: a held pose (fidx < 0) is copied, free pose f is
+// retracted by x [6 fidx[f] ..].  fidx and x: LDS or global memory.  By a 256-thread workgroup, as
+// tree_sum_256.
+__device__ __forceinline__ void lm_candidate_poses(int n, const int *fidx, const double *x, const float *poses,
+                                                   float *cand) {
+    for (int f = threadIdx.x; f < n; f += 256) {
+        const int fi = fidx[f];
+        if (fi < 0) {
+            for (int c = 0; c < 7; c++) cand[7 * f + c] = poses[7 * f + c];
+            continue;
+        }
+        retract_pose(x + 6 * fi, poses + 7 * f, cand + 7 * f);
+    }
+}
+
+// The per-problem results of a solver over many poses (k_ba_solve); thread 0 writes problem s.  A problem that
+// does not iterate reports its status with no iterations and both costs zero.
+struct LmResults {
+    double *__restrict__ cost0, *__restrict__ cost1;
+    int *__restrict__ iters, *__restrict__ status;
+};
+__device__ __forceinline__ void lm_report(const LmResults &R, int s, int status, int iters = 0, double cost0 = 0.0,
+                                          double cost1 = 0.0) {
+    if (threadIdx.x != 0) return;
+    R.status[s] = status;
+    R.iters[s] = iters;
+    R.cost0[s] = cost0;
+    R.cost1[s] = cost1;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -101,6 +101,20 @@ def test_parity_with_the_restatement(ctx, torch_cuda, B, F, cap, huber):
     assert (bits(dev["landmarks"])[~unseen] != bits(b["landmarks"])[~unseen]).any()
 
 
+@pytest.mark.parametrize("kw,decisions", [(dict(max_iters=12, rel_tol=0.0, lambda_max=1e-7), "AAAAr"),
+                                          (dict(max_iters=12, rel_tol=0.5), "AAAArrA")])
+def test_stop_rules(ctx, torch_cuda, kw, decisions):
+    """the two stop rules: lambda past lambda_max after a rejected step, and a relative decrease
+    below rel_tol on an accepted one; both end the loop before max_iters"""
+    import mvtrack
+
+    b = lr.ba_batch([lr.ba_scene(3, 4, 32)])
+    ref = reference(("stop", decisions), b, lr.params(**kw))
+    assert ["".join("A" if d else "r" for d in w) for w in ref["decisions"]] == [decisions]
+    assert ref["status"][0] == 0 and ref["iters"][0] == len(decisions) < kw["max_iters"]
+    same_bits(run_dev(ctx, torch_cuda, b, mvtrack.ba_params(**kw)), ref)
+
+
 def test_bitwise_properties(ctx, torch_cuda, monkeypatch):
     """twice the same; in place = out of place; a window's result does not depend on the batch, its
     index or the grid (300 windows on 2 workgroups: more windows than workgroups, slabs reused)"""

@@ -92,6 +92,21 @@ def test_parity_with_the_restatement(ctx, torch_cuda, B, N, huber):
         assert g.kind[5] == pr.DIRECTION and e[3:] == [0, 0, 0] and not np.array(A)[3:].any()
 
 
+@pytest.mark.parametrize("kw,decisions", [
+    (dict(max_iters=14, rel_tol=0.0, lambda_max=1e-7), ["AAAAr", "AAAr", "AAr"]),
+    (dict(max_iters=14, rel_tol=1e-2), ["AAAArrrrrrrArA", "AAArrrrrrArrAr", "AArrA"])])
+def test_stop_rules(ctx, torch_cuda, kw, decisions):
+    """the two stop rules: lambda past lambda_max after a rejected step, and a relative decrease
+    below rel_tol on an accepted one (graph 2; graphs 0 and 1 run into max_iters there)"""
+    import mvtrack
+
+    b = pr.parity_batch(3, 9)
+    ref = reference(("stop", decisions[0]), b, pr.params(**kw))
+    assert ["".join("A" if d else "r" for d in g) for g in ref["decisions"]] == decisions
+    assert (ref["status"] == 0).all() and list(ref["iters"]) == [len(d) for d in decisions]
+    same_bits(run_dev(ctx, torch_cuda, b, mvtrack.pg_params(**kw)), ref)
+
+
 def test_bitwise_properties(ctx, torch_cuda, monkeypatch):
     """twice the same; in place = out of place; a graph's result does not depend on the batch, its
     index or the grid (300 graphs on 2 workgroups: more graphs than workgroups, slabs reused)"""

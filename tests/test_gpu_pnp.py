@@ -174,6 +174,27 @@ def test_cap_equal_to_n(ctx, torch_cuda, cap):
     assert (ref["status"] == 0).all()
 
 
+@pytest.mark.parametrize("kw,rounds", [(dict(rel_tol=0.0, max_iters=14, lambda_max=1e-7), [3, 2]),
+                                       (dict(rel_tol=0.5, max_iters=14), [2, 1]),
+                                       (dict(rel_tol=0.0, max_iters=14, lambda_max=1e-7, huber_px=1.0), [7, 4])])
+def test_stop_rules(ctx, torch_cuda, monkeypatch, kw, rounds):
+    """the two stop rules of the refinement's LM: lambda past lambda_max after a rejected step, and a
+    relative decrease below rel_tol on an accepted one; every round ends before max_iters"""
+    b = stack([pr.scene(7, 65, outliers=0.3, noise_px=0.5)])
+    kw = dict(kw, hypotheses=32)
+    seen, lm_pose = [], pr.lm_pose
+
+    def counted(*a):
+        pose, iters = lm_pose(*a)
+        seen.append(iters)
+        return pose, iters
+
+    monkeypatch.setattr(pr, "lm_pose", counted)
+    ref = pr.solve_batch(b["pts3"], b["pts2"], b["n"], b["cams"], None, pr.params(**kw))
+    assert seen == rounds and max(rounds) < kw["max_iters"] and ref["status"][0] == 0
+    same(run_solve(ctx, torch_cuda, b, None, kw), ref)
+
+
 def prior_batch(B, n):
     """B problems; priors by turns: the truth, a wrong pose, a pose with a NaN"""
     key = ("prior", B, n)

@@ -3,6 +3,8 @@
 runs pose_from_matches and pose_batch on a fixed list of inputs once per library (a fresh child
 process each: mvtrack reads MV_LIB at import), writes T / num_matches / num_inliers / status to
 OUT_DIR/<library>.npz and counts the int32 words that differ.  Exit status 1 when any does.
+With --solvers as the first argument the inputs are the second list, solver_cases: the LM solvers
+(mv_ba_solve_dev, mv_pg_solve_dev, mv_pnp_solve_dev) on the small shapes of their bench tools.
 Build the other library with tools/build_variant.sh, or with make OUT= OBJDIR= in a git worktree."""
 import os
 import subprocess
@@ -75,6 +77,38 @@ def cases(torch, cx):
                k1.cpu().numpy(), idx.cpu().numpy(), 1024)
 
 
+def solver_cases(cx, dev):
+    """(name, every output of one call): tools/bench_lba.py at 32 x 16 x 1024, bench_pgo.py at 32 x 257
+    with one loop and with eight, bench_pnp.py at 32 x 1024 (gather and solve), the tools' own seeds
+    and default parameters -- more than 256 landmarks, nodes and pairs, which the parity tests stop
+    short of"""
+    sys.path[:0] = [os.path.join(ROOT, d) for d in ("oracle", "tests", "tools")]
+    import bench_lba
+    import bench_pgo
+    import bench_pnp
+    runs = [("lba_32x16x1024", bench_lba.run_shape, (32, 16, 1024, 101)),
+            ("pgo_32x257_loop", bench_pgo.run_shape, (32, 257, bench_pgo.LOOPS_8[:1], 0)),
+            ("pgo_32x257_loops8", bench_pgo.run_shape, (32, 257, bench_pgo.LOOPS_8, 1000)),
+            ("pnp_32x1024", bench_pnp.run_shape, (32, 1024, 102))]
+    for name, run, args in runs:
+        keep = {}
+        run(cx, dev, *args, keep=keep)
+        yield name, keep
+
+
+def child_solvers(out):
+    import mvtrack
+    import torch
+    dev, res = torch.device("cuda:0"), {}
+    cx = mvtrack.Context(0)
+    cx.set_stream(torch.cuda.current_stream())
+    for name, keep in solver_cases(cx, dev):
+        torch.cuda.synchronize()
+        for k, v in keep.items():
+            res[name + "." + k] = v.cpu().numpy()
+    np.savez(out, **res)
+
+
 def child(out):
     import mvtrack
     import torch
@@ -99,20 +133,25 @@ def child(out):
 
 
 if __name__ == "__main__":
-    if sys.argv[1] == "--child":
-        sys.exit(child(sys.argv[2]))
+    if sys.argv[1] in ("--child", "--child-solvers"):
+        sys.exit((child if sys.argv[1] == "--child" else child_solvers)(sys.argv[2]))
+    solvers = sys.argv[1] == "--solvers"
+    del sys.argv[1:1 + solvers]
     libs, out = sys.argv[1:3], sys.argv[3] if len(sys.argv) > 3 else "ab_tmp/ab_pose_bits"
     os.makedirs(out, exist_ok=True)
     npz = [os.path.join(out, os.path.basename(p)[:-3] + ".npz") for p in libs]
     for lib, f in zip(libs, npz):  # one fresh process per library, each under its own time limit
-        subprocess.run([sys.executable, os.path.abspath(__file__), "--child", f], check=True, timeout=300,
+        subprocess.run([sys.executable, os.path.abspath(__file__), "--child-solvers" if solvers else "--child", f],
+                       check=True, timeout=300,
                        env=dict(os.environ, MV_LIB=os.path.abspath(lib)))
     a, b = (np.load(f) for f in npz)
     assert sorted(a.files) == sorted(b.files)
     bad = 0
     for k in a.files:
-        d = int((a[k].view(np.int32) != b[k].view(np.int32)).sum())
+        wa, wb = a[k].view(np.int32), b[k].view(np.int32)  # float64 costs: two words each
+        d = int((wa != wb).sum())
         bad += d
-        print("%-28s words %6d differing %d   status %s" % (k, a[k].size, d, np.unique(a[k]) if k.endswith("st") else ""))
+        is_status = k.rsplit(".", 1)[-1] in ("st", "batch_st")
+        print("%-28s words %6d differing %d   status %s" % (k, wa.size, d, np.unique(a[k]) if is_status else ""))
     print("TOTAL differing words: %d (%s vs %s)" % (bad, *libs))
     sys.exit(1 if bad else 0)

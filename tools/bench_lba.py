@@ -28,7 +28,8 @@ import mvtrack  # noqa: E402
 SHAPES = ((2048, 5, 512), (32, 16, 1024))
 
 
-def run_shape(ctx, dev, B, F, cap, seed, baseline=False):
+def run_shape(ctx, dev, B, F, cap, seed, baseline=False, keep=None):
+    """keep: a dict that receives the last call's output tensors (tools/ab_pose_bits.py --solvers)"""
     import lba_reference as lr
 
     d = bench_tracks.gen(dev, B, F, cap, seed, redirect=0.0)
@@ -66,6 +67,8 @@ def run_shape(ctx, dev, B, F, cap, seed, baseline=False):
     tracks_ms, _ = bench_tracks.timed(tracks)
     ms, steps = bench_tracks.timed(solve)
     assert (status == 0).all().item() and int(fstatus.item()) == 0 and (bstatus == 0).all().item()
+    if keep is not None:
+        keep.update(poses=out_p, landmarks=out_l, cost_initial=c0, cost_final=c1, iters=iters, st=bstatus)
     nfac, solves = int(off[-1].item()), int(iters.sum().item())
     et = float((out_p[:, 2:, 4:] - d["poses"][:, 2:, 4:]).abs().max().item())
     rep = {"shape": [B, F, cap], "track_cap": track_cap, "factors": nfac, "solves": solves,

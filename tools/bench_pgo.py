@@ -27,7 +27,8 @@ LOOPS_8 = [(256, 0), (240, 16), (224, 32), (208, 48), (192, 64), (176, 80), (160
 SHAPES = ((32, 257, [(256, 0)]), (32, 257, LOOPS_8), (2048, 33, [(32, 0), (24, 8)]))
 
 
-def run_shape(ctx, dev, B, N, loops, seed, baseline=False):
+def run_shape(ctx, dev, B, N, loops, seed, baseline=False, keep=None):
+    """keep: a dict that receives the last call's output tensors (tools/ab_pose_bits.py --solvers)"""
     import pgo_reference as pr
 
     scenes = [pr.pg_scene(N, loops, sigma_r=2e-3, sigma_t=2e-2, weights=(100.0, 1.0), seed=seed + s, start="chained")
@@ -46,6 +47,8 @@ def run_shape(ctx, dev, B, N, loops, seed, baseline=False):
 
     ms, steps = bench_tracks.timed(solve, min_steps=5)
     assert (status == 0).all().item()
+    if keep is not None:
+        keep.update(poses=out, cost_initial=c0, cost_final=c1, iters=iters, st=status)
     solves, E = int(iters.sum().item()), len(scenes[0]["edge_i"])
     got = out.cpu().numpy()
     before = [pr.pair_errors(sc["poses"], sc["poses_true"], *loops[0])[1] for sc in scenes[:8]]

@@ -63,7 +63,8 @@ def gen(dev, B, n, seed):
                 inlier=~bad)
 
 
-def run_shape(ctx, dev, B, n, seed, compare=False):
+def run_shape(ctx, dev, B, n, seed, compare=False, keep=None):
+    """keep: a dict that receives the last call's output tensors (tools/ab_pose_bits.py --solvers)"""
     d = gen(dev, B, n, seed)
     i32, f32 = torch.int32, torch.float32
     e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)  # noqa: E731
@@ -101,6 +102,9 @@ def run_shape(ctx, dev, B, n, seed, compare=False):
     torch.cuda.synchronize()
     yard = mvtrack.profile_query("k_pose_ransac")
     mvtrack.profile_enable(False)
+    if keep is not None:
+        keep.update(pts3=pts3, pts2=pts2, count=count, pose=pose, inlier=inl, num_inliers=ni, best_hyp=bh, st=st,
+                    cost=cost)
     ok = st == 0
     got, true = pose[ok].double(), d["poses"][ok].double()
     sign = torch.where((got[:, :4] * true[:, :4]).sum(1) < 0, -1.0, 1.0)[:, None]
