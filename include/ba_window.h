@@ -63,7 +63,9 @@
  *
  * Out of scope: frames outside the window as fixed observers (their observations of the window's
  * landmarks are left out, so a landmark is held in place only by the window's own fixed poses);
- * marginalisation and priors; keyframe culling; choosing W; moving landmarks after mv_pg_solve_dev.
+ * marginalisation and priors; keyframe culling; choosing W.  Moving landmarks after mv_pg_solve_dev is
+ * map_correct.h's mv_map_move_landmarks_dev; its mv_map_fuse_dev joins the two sides of a closed loop,
+ * after which the covisibility here spans it.
  */
 #ifndef MV_BA_WINDOW_H
 #define MV_BA_WINDOW_H

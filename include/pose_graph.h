@@ -68,8 +68,9 @@
  * Limits: 2 <= nodes <= MV_PG_MAX_NODES, env_cap >= 1, batch * nodes < 2^31.
  *
  * Out of scope: Sim(3) and scale-drift states; 6 x 6 information matrices; choosing which loop
- * candidates to trust beyond the Huber loss; spreading the corrected poses to landmarks;
- * factorising one graph across several workgroups; fill-reducing orderings.
+ * candidates to trust beyond the Huber loss; factorising one graph across several workgroups;
+ * fill-reducing orderings.  Spreading the corrected poses to the landmarks is map_correct.h's step
+ * (mv_map_move_landmarks_dev takes the poses before and after this solve).
  */
 #ifndef MV_POSE_GRAPH_H
 #define MV_POSE_GRAPH_H

@@ -11,7 +11,8 @@
 //           and the workgroup count of a grid-stride solver.
 // A solver supplies what lm_run's Problem lists: linearize (its factor kind), step (its linear
 // solve and its candidate) and accept (its state copy).
-// quat_rot is also the R(q) of the triangulation (tr_midpoint.hpp) and of k_map_match.
+// quat_rot is also the R(q) of the triangulation (tr_midpoint.hpp), of k_map_match and of k_mc_move
+// (k_mapcorr.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>

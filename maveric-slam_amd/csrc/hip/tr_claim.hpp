@@ -4,7 +4,8 @@
 // (k_map_match: a keypoint accepts one landmark).
 // And block_rank, the rank of a flagged thread within its workgroup: the ballot compaction in
 // ascending order of k_tracks.hip, k_mapupd.hip, k_bawin.hip, k_pnp.hip (k_pnp_gather and
-// k_pnp_solve's staging) and k_map.hip (the emitted pairs); clampn for a count read from memory.
+// k_pnp_solve's staging), k_map.hip (the emitted pairs) and k_mapcorr.hip (k_mc_pairs); clampn for a
+// count read from memory.
 #pragma once
 #include <hip/hip_runtime.h>
 

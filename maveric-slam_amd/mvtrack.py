@@ -104,6 +104,11 @@ class MapParams(ctypes.Structure):
     _fields_ = [("radius_px", _D), ("min_depth", _D), ("thresh", _D), ("ratio", _D), ("width", _I), ("height", _I)]
 
 
+class MapCorrectParams(ctypes.Structure):
+    """mv_map_correct_params (include/map_correct.h)."""
+    _fields_ = [("split_rel", _D)]
+
+
 BA_MAX_POSES = 16  # MV_BA_MAX_POSES
 PNP_MAX_CAP = 1024  # MV_PNP_MAX_CAP
 PG_MAX_NODES = 512  # MV_PG_MAX_NODES
@@ -251,6 +256,10 @@ def lib():
             "mv_ba_window_select_dev": (_I, [_P, _P, _I, _I, _I, _I] + [_P] * 7),
             "mv_ba_window_factors_dev": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I] + [_P] * 15),
             "mv_ba_window_scatter_dev": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
+            "mv_map_correct_params_default": (None, [_P]),
+            "mv_map_move_landmarks_dev": (_I, [_P, _P, _I, _I, _I, _I, _I] + [_P] * 10),
+            "mv_map_fuse_pairs_dev": (_I, [_P, _I, _I, _I, _I, _I] + [_P] * 12),
+            "mv_map_fuse_dev": (_I, [_P, _I, _I, _I, _I, _I, _I] + [_P] * 17),
         }
         for name, (res, args) in sig.items():
             try:
@@ -515,6 +524,11 @@ def map_params(**kw):
 def ba_window_params(**kw):
     """mv_ba_window_params with its defaults (min_shared 15, n_fixed 2, min_obs 2)."""
     return _params(BaWindowParams, "mv_ba_window_params_default", kw)
+
+
+def map_correct_params(**kw):
+    """mv_map_correct_params with its default (split_rel 1e-2)."""
+    return _params(MapCorrectParams, "mv_map_correct_params_default", kw)
 
 
 def pg_envelope(nodes, edge_i, edge_j, node_fixed=None):
@@ -1028,6 +1042,57 @@ class Context:
                                            F if f_count is None else int(f_count), _t(poses), _t(cameras), _t(kp),
                                            _t(num_tracks), _t(track_first), _t(track_len), _t(next_obs), _t(status),
                                            _t(select), _t(landmarks), _t(ldmk_flags)), "map_triangulate")
+
+    # ---------------- map loop correction (include/map_correct.h) ----------------
+    map_correct_params = staticmethod(map_correct_params)
+
+    def map_move_landmarks(self, poses_old, poses_new, num_tracks, track_first, track_len, track_last, status,
+                           ldmk_flags, landmarks, retri, cap, f_count=None, params=None):
+        """Device tensors: poses_old / poses_new [B, F, 7] (the poses the landmarks were made with and
+        the corrected ones), the map state with cap keypoint slots per frame, ldmk_flags [B, track_cap]
+        -> landmarks [B, track_cap, 3] carried with their anchor frames in place, retri [B, track_cap]
+        int32: 1 where the track straddles the correction (map_triangulate's select)."""
+        B, F = poses_old.shape[0], poses_old.shape[1]
+        assert poses_new.shape == poses_old.shape == (B, F, 7) and landmarks.shape == (B, ldmk_flags.shape[1], 3)
+        assert retri.shape == ldmk_flags.shape == track_first.shape == track_len.shape == track_last.shape
+        p = params or map_correct_params()
+        check(lib().mv_map_move_landmarks_dev(self.h, ctypes.byref(p), B, F, int(cap), ldmk_flags.shape[1],
+                                              F if f_count is None else int(f_count), _t(poses_old), _t(poses_new),
+                                              _t(num_tracks), _t(track_first), _t(track_len), _t(track_last),
+                                              _t(status), _t(ldmk_flags), _t(landmarks), _t(retri)),
+              "map_move_landmarks")
+
+    def map_fuse_pairs(self, f_q, n_q, track_id, num_tracks, status, map_idx, pair_a, pair_b, count, f_count=None,
+                       pair_ldmk=None, pair_count=None, inlier=None):
+        """Device tensors: f_q / n_q [B] (the matched frame and its keypoint count), track_id
+        [B, F, cap], num_tracks / status [B], map_idx [B, track_cap] (map_match's match_idx for frame
+        f_q); optionally map_match's pair_ldmk [B, cap] and pair_count [B] with pnp_solve's inlier
+        [B, cap] -- all three or none -> pair_a / pair_b [B, cap] (landmark, the track that owns its
+        keypoint; ascending landmark, the tail -1), count [B] int32."""
+        B, F, cap = track_id.shape
+        assert pair_a.shape == pair_b.shape == (B, cap) and map_idx.shape[0] == B
+        check(lib().mv_map_fuse_pairs_dev(self.h, B, F, cap, map_idx.shape[1], F if f_count is None else int(f_count),
+                                          _t(f_q), _t(n_q), _t(track_id), _t(num_tracks), _t(status), _t(map_idx),
+                                          _t(pair_ldmk), _t(pair_count), _t(inlier), _t(pair_a), _t(pair_b),
+                                          _t(count)), "map_fuse_pairs")
+
+    def map_fuse(self, pair_a, pair_b, pair_count, status, num_tracks, track_id, track_first, track_len, next_obs,
+                 track_last, landmarks, ldmk_flags, touched, fused_into, n_fused, n_rejected, fuse_status,
+                 f_count=None):
+        """Merges the tracks of one point in the map state (track_id / next_obs [B, F, cap], track_first /
+        track_len / track_last [B, track_cap], landmarks [B, track_cap, 3], ldmk_flags [B, track_cap], all
+        updated in place).  Device tensors: pair_a / pair_b [B, pair_cap], pair_count [B] (map_fuse_pairs,
+        or any other source), status / num_tracks [B] -> touched [B, track_cap] (1 at each kept track:
+        map_triangulate's select), fused_into [B, track_cap] (the kept track at each dropped one, else
+        -1), n_fused / n_rejected / fuse_status [B] int32."""
+        B, F, cap = track_id.shape
+        assert next_obs.shape == (B, F, cap) and pair_a.shape == pair_b.shape and pair_a.shape[0] == B
+        assert touched.shape == fused_into.shape == ldmk_flags.shape == track_first.shape == track_last.shape
+        check(lib().mv_map_fuse_dev(self.h, B, F, cap, track_first.shape[1], F if f_count is None else int(f_count),
+                                    pair_a.shape[1], _t(pair_a), _t(pair_b), _t(pair_count), _t(status),
+                                    _t(num_tracks), _t(track_id), _t(track_first), _t(track_len), _t(next_obs),
+                                    _t(track_last), _t(landmarks), _t(ldmk_flags), _t(touched), _t(fused_into),
+                                    _t(n_fused), _t(n_rejected), _t(fuse_status)), "map_fuse")
 
     # ---------------- local BA windows (include/ba_window.h) ----------------
     ba_window_params = staticmethod(ba_window_params)
