@@ -63,9 +63,11 @@
  *
  * Out of scope: frames outside the window as fixed observers (their observations of the window's
  * landmarks are left out, so a landmark is held in place only by the window's own fixed poses);
- * marginalisation and priors; keyframe culling; choosing W.  Moving landmarks after mv_pg_solve_dev is
+ * marginalisation and priors; choosing W.  Moving landmarks after mv_pg_solve_dev is
  * map_correct.h's mv_map_move_landmarks_dev; its mv_map_fuse_dev joins the two sides of a closed loop,
- * after which the covisibility here spans it.
+ * after which the covisibility here spans it.  Keyframe culling is map_cull.h's
+ * mv_map_cull_frames_dev: a culled frame's slots leave track_id (mv_map_cull_dev), so it drops out of
+ * every covisibility count and window selection here without an eligible mask.
  */
 #ifndef MV_BA_WINDOW_H
 #define MV_BA_WINDOW_H

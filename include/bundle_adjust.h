@@ -57,8 +57,9 @@
  * before capturing in a graph) and scale with the launch's workgroup count, not with batch.
  * Limits: 1 <= frames <= MV_BA_MAX_POSES, batch * frames and batch * track_cap < 2^31.
  *
- * Out of scope: marginalisation and priors; re-numbering landmarks; anything feeding
- * mv_lba_schur_dev.  Choosing a window of a sequence longer than MV_BA_MAX_POSES frames, gathering it
+ * Out of scope: marginalisation and priors; anything feeding mv_lba_schur_dev.  Re-numbering the
+ * landmarks to drop dead ones is mv_map_compact_dev and rejecting single observations as outliers
+ * mv_map_screen_obs_dev with mv_map_cull_dev (map_cull.h), between solves, not part of one.  Choosing a window of a sequence longer than MV_BA_MAX_POSES frames, gathering it
  * into this layout and writing its poses back is ba_window.h, not part of the solve; triangulating and
  * flagging landmarks again from all their observations is mv_map_triangulate_dev (map_update.h).
  */

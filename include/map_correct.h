@@ -90,8 +90,9 @@
  * split_rel finite and >= 0.  A bad argument returns MV_ERR_INVALID_ARG and launches nothing.
  *
  * Out of scope: Sim(3) and scale correction (the move is rigid per anchor frame); undoing a fusion
- * that triangulates badly (fused_into tells the caller what was merged); compacting track numbers;
- * choosing which frames to search again after a loop closure.
+ * that triangulates badly (fused_into tells the caller what was merged); choosing which frames to
+ * search again after a loop closure.  The numbers of the dropped tracks are taken back by
+ * mv_map_compact_dev (map_cull.h).
  */
 #ifndef MV_MAP_CORRECT_H
 #define MV_MAP_CORRECT_H

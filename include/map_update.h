@@ -90,10 +90,10 @@
  * 1 <= f_count <= frames; kp 8-byte aligned.  A bad argument returns MV_ERR_INVALID_ARG and launches
  * nothing.
  *
- * Out of scope: removing observations or tracks, keyframe choice (the covisibility a choice would
- * read is mv_map_covisibility_dev, ba_window.h, and mv_ba_window_select_dev's eligible mask is where a
- * choice of keyframes enters the local BA).  Merging two tracks of one point and moving landmarks
- * after mv_pg_solve_dev are map_correct.h's (mv_map_fuse_dev, mv_map_move_landmarks_dev).
+ * Out of scope here and done elsewhere: removing observations, tracks and redundant frames and taking
+ * back the numbers of dead tracks (so that MV_ERR_CAPACITY in step 4 is a matter of the live map, not
+ * of its history) are map_cull.h's; merging two tracks of one point and moving landmarks after
+ * mv_pg_solve_dev are map_correct.h's (mv_map_fuse_dev, mv_map_move_landmarks_dev).
  */
 #ifndef MV_MAP_UPDATE_H
 #define MV_MAP_UPDATE_H

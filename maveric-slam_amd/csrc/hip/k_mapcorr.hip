@@ -22,11 +22,10 @@
 #include <limits.h>
 #include <math.h>
 
-#include <initializer_list>
-
 #include "map_correct.h"
 #include "mv_internal.hpp"
 #include "mv_lm.hpp"
+#include "tr_chain.hpp"
 #include "tr_claim.hpp"
 
 namespace {
@@ -35,6 +34,8 @@ constexpr int NT = 256;
 constexpr int NE = 1024;  // a sequence has one workgroup: as wide as a workgroup gets
 constexpr int NONE = INT_MAX;
 
+using mv::no_overlap;
+using tr::chain_whole;
 using tr::clampn;
 
 // a global word other threads of the workgroup wrote: read past the vector L1
@@ -172,22 +173,6 @@ __global__ __launch_bounds__(NE) void k_mc_pairs(int F, int cap, int track_cap, 
     if (tid == 0) count[s] = kept;
 }
 
-// true when the chain of track t is whole: track_len slots by mv_map_triangulate_dev's walk below
-// lim, ending at track_last, every slot naming t.  Frames ascend strictly, so the walk ends.
-__device__ __forceinline__ bool chain_whole(const int *tid_s, const int *next_obs, int cap, int lim, int t, int first,
-                                            int len, int last) {
-    if (len <= 0 || first < 0 || first >= lim) return false;
-    int g = first, n = 0;
-    for (;;) {
-        if (tid_s[g] != t) return false;
-        if (++n >= len) break;
-        const int nx = next_obs[g];
-        if (nx < 0 || nx >= lim || nx / cap <= g / cap) return false;
-        g = nx;
-    }
-    return g == last;
-}
-
 __global__ __launch_bounds__(NE) void k_mc_fuse(int F, int cap, int track_cap, int f_count, int pair_cap,
                                                 const int *__restrict__ pair_a, const int *__restrict__ pair_b,
                                                 const int *__restrict__ pair_count, const int *__restrict__ status,
@@ -297,23 +282,6 @@ __global__ __launch_bounds__(NE) void k_mc_fuse(int F, int cap, int track_cap, i
 bool shape_ok(int batch, int frames, int cap, int track_cap) {
     return batch > 0 && frames >= 2 && cap >= 1 && cap <= MV_TRACKS_MAX_CAP && track_cap >= 1 &&
            (long)batch * frames * cap < (1l << 31) && (long)batch * track_cap < (1l << 31);
-}
-
-// an array of a call: no array that is written may overlap another one
-struct Span {
-    const void *p;
-    size_t bytes;
-    bool written;
-};
-
-bool no_overlap(std::initializer_list<Span> spans) {
-    for (const Span *a = spans.begin(); a != spans.end(); a++)
-        for (const Span *b = a + 1; b != spans.end(); b++) {
-            if (!(a->written || b->written) || !a->p || !b->p) continue;
-            const uintptr_t a0 = (uintptr_t)a->p, b0 = (uintptr_t)b->p;
-            if (a0 < b0 + b->bytes && b0 < a0 + a->bytes) return false;
-        }
-    return true;
 }
 
 }  // namespace

@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stddef.h>
 
+#include <initializer_list>
+
 #include "maveric_hip.h"
 #include "mv_carve.hpp"
 
@@ -85,6 +87,23 @@ bool carve(void *(*buffer)(mv_context *, size_t), mv_context *ctx, F layout) {
     Carve c{static_cast<char *>(buffer(ctx, need.bytes()))};
     if (c.base) layout(c);
     return c.base != nullptr;
+}
+
+// an array of a call (k_mapcorr.hip, k_mapcull.hip): no array that is written may overlap another one
+struct Span {
+    const void *p;  // nullptr: an optional array that was not given
+    size_t bytes;
+    bool written;
+};
+
+inline bool no_overlap(std::initializer_list<Span> spans) {
+    for (const Span *a = spans.begin(); a != spans.end(); a++)
+        for (const Span *b = a + 1; b != spans.end(); b++) {
+            if (!(a->written || b->written) || !a->p || !b->p) continue;
+            const uintptr_t a0 = (uintptr_t)a->p, b0 = (uintptr_t)b->p;
+            if (a0 < b0 + b->bytes && b0 < a0 + a->bytes) return false;
+        }
+    return true;
 }
 
 // Wait for every stream this context has issued work on (its own stream -- which waits on every

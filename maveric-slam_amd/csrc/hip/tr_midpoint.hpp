@@ -3,7 +3,8 @@
 // observations along next_obs), so that the two cannot drift apart.  Every line follows
 // tests/tracks_reference.py's triangulate_track operation for operation; all arithmetic float64,
 // no contraction (-ffp-contract=off).  A kernel walks its observations twice: add() per observation
-// and solve(), then check() per observation on the solved point.
+// and solve(), then check() per observation on the solved point.  k_mapcull.hip (k_cl_screen) walks
+// them once with reproject() on the stored landmark.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -26,6 +27,20 @@ __device__ __forceinline__ void load_obs(Obs &o, const float *__restrict__ pose,
     const float2 p = *reinterpret_cast<const float2 *>(kp + 2 * node);
     o.u = (double)p.x;
     o.v = (double)p.y;
+}
+
+// One observation against a point X: its depth p2 and reprojection residual (du, dv) -- the second
+// loop of triangulate_track.  Midpoint::check reads the landmark bits off it, k_mapcull.hip's screen
+// the per-observation verdict.
+__device__ __forceinline__ void reproject(const Obs &cur, double X0, double X1, double X2, double &p2, double &du,
+                                          double &dv) {
+    double R[9];
+    mv::quat_rot(cur.q, R);
+    const double p0 = ((R[0] * X0 + R[1] * X1) + R[2] * X2) + cur.q[4];
+    const double p1 = ((R[3] * X0 + R[4] * X1) + R[5] * X2) + cur.q[5];
+    p2 = ((R[6] * X0 + R[7] * X1) + R[8] * X2) + cur.q[6];
+    du = (cur.k[0] * (p0 / p2) + cur.k[2]) - cur.u;
+    dv = (cur.k[1] * (p1 / p2) + cur.k[3]) - cur.v;
 }
 
 struct Midpoint {
@@ -87,14 +102,9 @@ struct Midpoint {
     // the depth and reprojection bits of one observation on the solved point (mr2 = max_reproj^2)
     __device__ __forceinline__ int check(const Obs &cur, double min_depth, double mr2) const {
         int flags = 0;
-        double R[9];
-        mv::quat_rot(cur.q, R);
-        const double p0 = ((R[0] * X0 + R[1] * X1) + R[2] * X2) + cur.q[4];
-        const double p1 = ((R[3] * X0 + R[4] * X1) + R[5] * X2) + cur.q[5];
-        const double p2 = ((R[6] * X0 + R[7] * X1) + R[8] * X2) + cur.q[6];
+        double p2, du, dv;
+        reproject(cur, X0, X1, X2, p2, du, dv);
         if (p2 < min_depth) flags |= MV_LDMK_BEHIND;
-        const double du = (cur.k[0] * (p0 / p2) + cur.k[2]) - cur.u;
-        const double dv = (cur.k[1] * (p1 / p2) + cur.k[3]) - cur.v;
         if (du * du + dv * dv > mr2) flags |= MV_LDMK_REPROJ;
         return flags;
     }

@@ -1,7 +1,7 @@
 // tr_scan.hpp -- integer scans by one 256-thread workgroup.  Users: k_tracks.hip (k_tr_scan: track
 // numbering, factor offsets), k_bawin.hip (k_bw_scan: the window's factor offsets), k_pgo.hip
-// (k_pg_solve's prologue: incidence lists, free nodes, envelope and column lists) and k_map.hip
-// (k_map_match: cell starts, the tile's work list).
+// (k_pg_solve's prologue: incidence lists, free nodes, envelope and column lists), k_map.hip
+// (k_map_match: cell starts, the tile's work list) and k_mapcull.hip (k_cl_rows: the new track numbers).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -109,6 +109,12 @@ class MapCorrectParams(ctypes.Structure):
     _fields_ = [("split_rel", _D)]
 
 
+class MapCullParams(ctypes.Structure):
+    """mv_map_cull_params (include/map_cull.h)."""
+    _fields_ = [("max_reproj_px", _D), ("min_depth", _D), ("worst_only", _I), ("min_obs", _I), ("stale_age", _I),
+                ("stale_min_obs", _I), ("min_views", _I), ("redundant_num", _I), ("redundant_den", _I)]
+
+
 BA_MAX_POSES = 16  # MV_BA_MAX_POSES
 PNP_MAX_CAP = 1024  # MV_PNP_MAX_CAP
 PG_MAX_NODES = 512  # MV_PG_MAX_NODES
@@ -260,6 +266,12 @@ def lib():
             "mv_map_move_landmarks_dev": (_I, [_P, _P, _I, _I, _I, _I, _I] + [_P] * 10),
             "mv_map_fuse_pairs_dev": (_I, [_P, _I, _I, _I, _I, _I] + [_P] * 12),
             "mv_map_fuse_dev": (_I, [_P, _I, _I, _I, _I, _I, _I] + [_P] * 17),
+            "mv_map_cull_params_default": (None, [_P]),
+            "mv_map_screen_obs_dev": (_I, [_P, _P, _I, _I, _I, _I, _I] + [_P] * 12),
+            "mv_map_stale_tracks_dev": (_I, [_P, _P, _I, _I, _I, _I, _I] + [_P] * 6),
+            "mv_map_cull_frames_dev": (_I, [_P, _P, _I, _I, _I, _I, _I] + [_P] * 8),
+            "mv_map_cull_dev": (_I, [_P, _P, _I, _I, _I, _I, _I] + [_P] * 17),
+            "mv_map_compact_dev": (_I, [_P, _I, _I, _I, _I] + [_P] * 11),
         }
         for name, (res, args) in sig.items():
             try:
@@ -529,6 +541,12 @@ def ba_window_params(**kw):
 def map_correct_params(**kw):
     """mv_map_correct_params with its default (split_rel 1e-2)."""
     return _params(MapCorrectParams, "mv_map_correct_params_default", kw)
+
+
+def map_cull_params(**kw):
+    """mv_map_cull_params with its defaults (max_reproj_px 2, min_depth 0.1, worst_only 0, min_obs 2,
+    stale_age 2, stale_min_obs 3, min_views 3, redundant 9 / 10)."""
+    return _params(MapCullParams, "mv_map_cull_params_default", kw)
 
 
 def pg_envelope(nodes, edge_i, edge_j, node_fixed=None):
@@ -1093,6 +1111,85 @@ class Context:
                                     _t(num_tracks), _t(track_id), _t(track_first), _t(track_len), _t(next_obs),
                                     _t(track_last), _t(landmarks), _t(ldmk_flags), _t(touched), _t(fused_into),
                                     _t(n_fused), _t(n_rejected), _t(fuse_status)), "map_fuse")
+
+    # ---------------- map culling (include/map_cull.h) ----------------
+    map_cull_params = staticmethod(map_cull_params)
+
+    def map_screen_observations(self, poses, cameras, kp, num_tracks, track_first, track_len, next_obs, status,
+                                landmarks, ldmk_flags, remove, n_bad, f_count=None, params=None):
+        """Device tensors: poses [B, F, 7], cameras [B, F, 4], kp [B, F, cap, 2], the map state and its
+        landmarks [B, track_cap, 3] / ldmk_flags [B, track_cap] -> remove [B, F, cap] int32 (1 at every
+        observation that disagrees with its landmark; with params.worst_only only each track's worst),
+        n_bad [B] int32."""
+        B, F, cap = next_obs.shape
+        assert kp.shape == (B, F, cap, 2) and remove.shape == (B, F, cap) and n_bad.shape == (B,)
+        assert landmarks.shape == (B, ldmk_flags.shape[1], 3) and track_first.shape == ldmk_flags.shape
+        p = params or map_cull_params()
+        check(lib().mv_map_screen_obs_dev(self.h, ctypes.byref(p), B, F, cap, track_first.shape[1],
+                                          F if f_count is None else int(f_count), _t(poses), _t(cameras), _t(kp),
+                                          _t(num_tracks), _t(track_first), _t(track_len), _t(next_obs), _t(status),
+                                          _t(landmarks), _t(ldmk_flags), _t(remove), _t(n_bad)),
+              "map_screen_observations")
+
+    def map_stale_tracks(self, num_tracks, track_len, track_last, status, ldmk_flags, drop, frames, cap, f_count=None,
+                         params=None):
+        """Device tensors: num_tracks / status [B], track_len / track_last / ldmk_flags [B, track_cap] of a
+        map with `frames` frames of `cap` slots -> drop [B, track_cap] int32: 1 at every track that ended
+        more than params.stale_age frames ago and is flagged or shorter than params.stale_min_obs."""
+        B, L = track_len.shape
+        assert drop.shape == track_last.shape == ldmk_flags.shape == (B, L)
+        p = params or map_cull_params()
+        check(lib().mv_map_stale_tracks_dev(self.h, ctypes.byref(p), B, int(frames), int(cap), L,
+                                            int(frames) if f_count is None else int(f_count), _t(num_tracks),
+                                            _t(track_len), _t(track_last), _t(status), _t(ldmk_flags), _t(drop)),
+              "map_stale_tracks")
+
+    def map_cull_frames(self, track_id, num_tracks, status, ldmk_flags, remove, frame_culled, n_culled, protect=None,
+                        f_count=None, params=None):
+        """The greedy keyframe cull.  Device tensors: track_id [B, F, cap], num_tracks / status [B],
+        ldmk_flags [B, track_cap], optionally protect [B, F] (nonzero: never culled); remove [B, F, cap]
+        is in/out (the mask so far; the culled frames' slots are added) -> frame_culled [B, F], n_culled
+        [B] int32."""
+        B, F, cap = track_id.shape
+        assert remove.shape == (B, F, cap) and frame_culled.shape == (B, F) and n_culled.shape == (B,)
+        assert protect is None or protect.shape == (B, F)
+        p = params or map_cull_params()
+        check(lib().mv_map_cull_frames_dev(self.h, ctypes.byref(p), B, F, cap, ldmk_flags.shape[1],
+                                           F if f_count is None else int(f_count), _t(track_id), _t(num_tracks),
+                                           _t(status), _t(ldmk_flags), _t(protect), _t(remove), _t(frame_culled),
+                                           _t(n_culled)), "map_cull_frames")
+
+    def map_cull(self, remove, drop, status, num_tracks, track_id, track_first, track_len, next_obs, track_last,
+                 landmarks, ldmk_flags, touched, dropped, n_obs_removed, n_dropped, n_rejected, cull_status,
+                 f_count=None, params=None):
+        """Takes the marked observations (remove [B, F, cap] or None) and tracks (drop [B, track_cap] or
+        None) out of the map state (track_id / next_obs [B, F, cap], track_first / track_len / track_last
+        [B, track_cap], landmarks [B, track_cap, 3], ldmk_flags [B, track_cap], all updated in place) ->
+        touched [B, track_cap] (1 at each shortened track: map_triangulate's select), dropped
+        [B, track_cap], n_obs_removed / n_dropped / n_rejected / cull_status [B] int32."""
+        B, F, cap = track_id.shape
+        assert next_obs.shape == (B, F, cap) and (remove is None or remove.shape == (B, F, cap))
+        assert touched.shape == dropped.shape == ldmk_flags.shape == track_first.shape == track_last.shape
+        assert drop is None or drop.shape == touched.shape
+        p = params or map_cull_params()
+        check(lib().mv_map_cull_dev(self.h, ctypes.byref(p), B, F, cap, track_first.shape[1],
+                                    F if f_count is None else int(f_count), _t(remove), _t(drop), _t(status),
+                                    _t(num_tracks), _t(track_id), _t(track_first), _t(track_len), _t(next_obs),
+                                    _t(track_last), _t(landmarks), _t(ldmk_flags), _t(touched), _t(dropped),
+                                    _t(n_obs_removed), _t(n_dropped), _t(n_rejected), _t(cull_status)), "map_cull")
+
+    def map_compact(self, status, track_id, num_tracks, track_first, track_len, track_last, landmarks, ldmk_flags,
+                    new_id, old_id, n_live):
+        """Renumbers the live tracks 0, 1, ... in place (track_id [B, F, cap], num_tracks [B], track_first /
+        track_len / track_last / ldmk_flags [B, track_cap], landmarks [B, track_cap, 3]; next_obs holds
+        slots and stays) -> new_id / old_id [B, track_cap] (mutually inverse, -1 elsewhere; per-track
+        data of the caller's moves as x[old_id]), n_live [B] int32."""
+        B, F, cap = track_id.shape
+        assert new_id.shape == old_id.shape == ldmk_flags.shape == track_first.shape == track_last.shape
+        assert landmarks.shape == (B, track_first.shape[1], 3) and n_live.shape == (B,)
+        check(lib().mv_map_compact_dev(self.h, B, F, cap, track_first.shape[1], _t(status), _t(track_id),
+                                       _t(num_tracks), _t(track_first), _t(track_len), _t(track_last), _t(landmarks),
+                                       _t(ldmk_flags), _t(new_id), _t(old_id), _t(n_live)), "map_compact")
 
     # ---------------- local BA windows (include/ba_window.h) ----------------
     ba_window_params = staticmethod(ba_window_params)
